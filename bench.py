@@ -25,11 +25,18 @@ Frames are rendered on the device into HBM before the timed region.  `value` =
 127.0.0.1) before anything touches a GPU; under torchrun WORLD_SIZE must equal
 --gpus, and fewer visible GPUs than --gpus is an error, never a silent N=1 run.
 
-The JSON line also carries `roofline` (dominant kernel: algorithmic bytes per
+A plain run sets up, warms up, times `--steps` steps and prints the headline
+JSON line (`value`, `ms_per_step`, the static configuration).  `--dump-outputs
+DIR` also writes what the last timed step left in the gathered result slots
+(dump_outputs below).  Everything else is behind `--full`: the line then also
+carries `roofline` (dominant kernel: algorithmic bytes per
 launch / HIP-event-timed average launch duration vs 8 TB/s, plus the VALU
-issue fraction from the committed PMC pass) and `cpu_baseline` (the oracle/
+issue fraction from the committed PMC pass), `cpu_baseline` (the oracle/
 CPU restatement on the host cores, 1 thread and all threads, on a bounded
-sample of the same workload).
+sample of the same workload), the results check, the single-frame latency and
+the side measurements (C4, undistort, stereo, DBoW2, the tracking searches,
+the drop-in call sites); the `--no-*`, `--cpu-sample` and `--latency-frames`
+options trim that run.
 """
 import argparse
 import json
@@ -87,7 +94,15 @@ def parse():
     ap.add_argument("--no-c4", action="store_true", help="skip the C4 (TUM 640x480, 2000 features) throughput line")
     ap.add_argument("--latency-frames", type=int, default=200,
                     help="single-frame latency leg: frames timed one at a time through the host C ABI (0 = skip)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the per-stage roofline pass, the results check, the CPU "
+                         "baseline, the latency leg and the side measurements (off: the headline line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results (rank 0's gathered slots) as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def free_port():
@@ -202,6 +217,17 @@ def main():
     elapsed = time.perf_counter() - t0
     check_all()
     elapsed = D.max_over_ranks(elapsed, dev)
+    ms_per_step = elapsed * 1000.0 / args.steps
+    fps = n_seq / (elapsed / args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(shard, args.dump_outputs)
+    line = headline(args, world, n_seq, n_own, F_ext, n_chunks, P, shard, fps, ms_per_step, render_s, graph_ok)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
     # roofline: the same K steps again with hipEvents around every stage launch
     # (a stage event between two kernels adds ~10 us of dispatch gap, so they
     # stay out of the throughput run)
@@ -222,9 +248,6 @@ def main():
             stage_ms["rccl_gather"] = float(np.mean([a.elapsed_time(b) for a, b in gather_ms]))
         if world > 1:
             dist.barrier()
-
-    ms_per_step = elapsed * 1000.0 / args.steps
-    fps = n_seq / (elapsed / args.steps)
 
     # ------------------------------------------------ results check: rank 0 holds every frame's slot
     seq_check = None
@@ -401,46 +424,19 @@ def main():
         lat["cpu_port_ms"] = round(cpu_lat, 3)
         lat["speedup_vs_cpu_port"] = round(cpu_lat / lat["median_ms"], 2)
     if rank == 0:
-        wl = (f"C5 offline sequence: {n_seq} frames (EuRoC MH01..05 length) sharded over {world} GPU(s), per frame "
-              f"C2 extract + dense Hamming (k vs k-1) + C3 SparseImgAlign levels 3..1, device-packed result slots "
-              f"gathered to rank 0 over RCCL") if args.workload == "c5" else \
-             (f"C2 batch: {args.batch} frames per GPU, extract + dense Hamming (k vs k-1) + C3 SparseImgAlign "
-              f"levels 3..1 + result slots")
-        line = {
-            "metric": "frames/sec ORB-extract+SparseImageAlign, 752x480, 1000 feat",
-            "value": round(fps, 2),
-            "unit": "frames/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True,
-            "scaling": "strong" if args.workload == "c5" else "weak",
-            "vs_baseline": None,
-            "dtype": "u8",
-            "data": "synthetic (seeded textured-plane renders on the device, EuRoC intrinsics; no dataset)",
-            "config": {"workload": wl, "sequence_frames": n_seq, "frames_per_gpu": n_own,
-                       "frames_extracted_per_gpu": F_ext, "chunks": n_chunks, "image": f"{W}x{H}", "nfeatures": nf, "scale_factor": sf,
-                       "nlevels": nl, "fast_th": [ini, mn], "align_pairs_per_gpu": P,
-                       "mean_keypoints": round(N, 1), "mean_align_visible": round(nv, 1),
-                       "mean_fast_candidates": round(float(cand.sum()) / F, 1),
-                       "mean_fast_candidates_per_level": [round(float(c) / F, 1) for c in cand],
-                       "mean_keypoints_per_level": [round(float(c) / F, 1) for c in selk],
-                       "parallelism": f"frame-sharded x{world} (contiguous shards + 1-frame halo)",
-                       "collective": (f"RCCL gather of result slots to rank 0 (torch.distributed.gather), "
-                                      f"{n_chunks} chunk(s), each gathered on a communication stream while the "
-                                      f"next chunk computes") if world > 1 else "none (N=1: rank 0 is the root)",
-                       "schedule": (args.schedule if (args.schedule == "pipe" or not shard.chunks)
-                                    else "chunked (each chunk serial)"),
-                       "schedule_stage_timing": "serial",
-                       "schedule_note": ("value times the steps under `schedule`; roofline.stages_ms comes from "
-                                         "a separate pass of the same steps (same chunk batches) in the serial "
-                                         "schedule (one kernel on the GPU at a time), so the stage times sum to "
-                                         "that pass's step, not to ms_per_step"),
-                       "hip_graph": graph_ok},
+        line["config"].update({
+            "mean_keypoints": round(N, 1), "mean_align_visible": round(nv, 1),
+            "mean_fast_candidates": round(float(cand.sum()) / F, 1),
+            "mean_fast_candidates_per_level": [round(float(c) / F, 1) for c in cand],
+            "mean_keypoints_per_level": [round(float(c) / F, 1) for c in selk],
+            "schedule_stage_timing": "serial",
+            "schedule_note": ("value times the steps under `schedule`; roofline.stages_ms comes from "
+                              "a separate pass of the same steps (same chunk batches) in the serial "
+                              "schedule (one kernel on the GPU at a time), so the stage times sum to "
+                              "that pass's step, not to ms_per_step")})
+        line.update({
             "roofline": roof,
             "pipeline_gbps_model": round(pipeline_gbps, 2),
-            "render_s": round(render_s, 2),
             "sequence_check": seq_check,
             "cpu_baseline": cpu,
             "latency": lat,
@@ -449,10 +445,82 @@ def main():
             "dropin_call_sites": dropin,
             "next_rows": {"undistort_remap": und_line, "search_local_points_direct": direct_line,
                           "stereo_matches": stereo_line, "dbow2_transform": bow_line},
-        }
+        })
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+def headline(args, world, n_seq, n_own, F_ext, n_chunks, P, shard, fps, ms_per_step, render_s, graph_ok):
+    """The result line of a plain run: the headline figure of the timed steps and the
+    configuration they ran under.  `--full` adds its measurements to this line."""
+    W, H, nf, sf, nl, ini, mn = C2
+    wl = (f"C5 offline sequence: {n_seq} frames (EuRoC MH01..05 length) sharded over {world} GPU(s), per frame "
+          f"C2 extract + dense Hamming (k vs k-1) + C3 SparseImgAlign levels 3..1, device-packed result slots "
+          f"gathered to rank 0 over RCCL") if args.workload == "c5" else \
+         (f"C2 batch: {args.batch} frames per GPU, extract + dense Hamming (k vs k-1) + C3 SparseImgAlign "
+          f"levels 3..1 + result slots")
+    return {
+        "metric": "frames/sec ORB-extract+SparseImageAlign, 752x480, 1000 feat",
+        "value": round(fps, 2),
+        "unit": "frames/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True,
+        "scaling": "strong" if args.workload == "c5" else "weak",
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": "synthetic (seeded textured-plane renders on the device, EuRoC intrinsics; no dataset)",
+        "full": bool(args.full),
+        "config": {"workload": wl, "sequence_frames": n_seq, "frames_per_gpu": n_own,
+                   "frames_extracted_per_gpu": F_ext, "chunks": n_chunks, "image": f"{W}x{H}", "nfeatures": nf,
+                   "scale_factor": sf, "nlevels": nl, "fast_th": [ini, mn], "align_pairs_per_gpu": P,
+                   "parallelism": f"frame-sharded x{world} (contiguous shards + 1-frame halo)",
+                   "collective": (f"RCCL gather of result slots to rank 0 (torch.distributed.gather), "
+                                  f"{n_chunks} chunk(s), each gathered on a communication stream while the "
+                                  f"next chunk computes") if world > 1 else "none (N=1: rank 0 is the root)",
+                   "schedule": (args.schedule if (args.schedule == "pipe" or not shard.chunks)
+                                else "chunked (each chunk serial)"),
+                   "hip_graph": graph_ok},
+        "render_s": round(render_s, 2),
+    }
+
+
+DUMP_SAMPLE_BYTES = 48 << 20  # keypoints + descriptors of the sampled frames, as float32
+
+
+def dump_outputs(shard, path):
+    """What the last timed step handed to its caller: rank 0's gathered result slots
+    (include/ygzfe.h, YGZFE_SLOT_*), decoded into DIR/<name>.npy.
+      header.npy         float64 [n_seq, 12]: n_kps, n_visible, T_cur_prev q[4] t[3], chi2, frame index,
+                         has_align, for every frame of the sequence;
+      sample_frames.npy  float64 [K]: the frames whose rows follow, a fixed seeded sample (every frame
+                         when they all fit in DUMP_SAMPLE_BYTES);
+      keypoints.npy      float32 [K, cap, 7]: x, y, size, angle, response, octave, class_id (rows >= n_kps 0);
+      descriptors.npy    float32 [K, cap, 32]: the rBRIEF bytes."""
+    import torch
+    from ygzfe import dist as D
+    full = shard.root_slots()
+    n_seq, cap = int(full.shape[0]), shard.cap
+    hdr = full[:, :D.SLOT_HEADER].contiguous().cpu().numpy()
+    hf, hi = hdr.view(np.float32), hdr.view(np.int32)
+    header = np.empty((n_seq, 12), np.float64)
+    header[:, 0:2] = hi[:, 0:2]
+    header[:, 2:10] = hf[:, 2:10]
+    header[:, 10:12] = hi[:, 10:12]
+    k = min(n_seq, max(1, DUMP_SAMPLE_BYTES // (cap * (7 + 32) * 4)))
+    idx = np.sort(np.random.default_rng(0).choice(n_seq, k, replace=False))
+    rows = full[torch.from_numpy(idx).to(full.device)].cpu().numpy()
+    kp = np.ascontiguousarray(rows[:, D.SLOT_HEADER:D.SLOT_HEADER + cap * 28]).reshape(k, cap, 28)
+    keypoints = kp.view(np.float32).copy()
+    keypoints[:, :, 5:] = kp.view(np.int32)[:, :, 5:]  # octave, class_id
+    desc = rows[:, D.SLOT_HEADER + cap * 28:D.SLOT_HEADER + cap * 60].reshape(k, cap, 32).astype(np.float32)
+    os.makedirs(path, exist_ok=True)
+    for name, a in (("header", header), ("sample_frames", idx.astype(np.float64)), ("keypoints", keypoints),
+                    ("descriptors", desc)):
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 # the resource that binds each stage below its HBM roofline (measured: DESIGN.md §4)

@@ -11,5 +11,5 @@ else
 fi
 timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
 if [ -n "$BENCH" ]; then
-  timeout -k 10 400 python bench.py $BENCH > $O/bench.json 2> $O/bench.err
+  timeout -k 10 400 python bench.py --full $BENCH > $O/bench.json 2> $O/bench.err
 fi

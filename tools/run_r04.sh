@@ -12,10 +12,10 @@ else
 fi
 timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
 if [ -n "$BENCH" ]; then
-  timeout -k 10 400 python bench.py $BENCH > $O/bench.json 2> $O/bench.err
+  timeout -k 10 400 python bench.py --full $BENCH > $O/bench.json 2> $O/bench.err
 fi
 if [ -n "$PROF" ]; then
   cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python bench.py --steps 5 --warmup 2 > $O/prof_bench.json 2> $O/prof_bench.err
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python bench.py --full --steps 5 --warmup 2 > $O/prof_bench.json 2> $O/prof_bench.err
   python tools/prof_summary.py $(find $O/prof -name '*kernel_stats.csv') > $O/kernel_summary.txt 2>&1 || true
 fi

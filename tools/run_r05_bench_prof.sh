@@ -4,5 +4,5 @@
 set -e
 O=gpurun_out/${1:-r05bp}
 mkdir -p $O
-timeout -k 10 500 python bench.py > $O/bench.json 2> $O/bench.err
+timeout -k 10 500 python bench.py --full > $O/bench.json 2> $O/bench.err
 bash tools/run_r05_prof_serial.sh ${1:-r05bp}

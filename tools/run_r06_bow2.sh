@@ -9,4 +9,4 @@ timeout -k 10 300 python -u -m pytest -x -q --timeout 200 --timeout-method threa
 timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/p -o run -- python3 tools/mb_bow_single.py 200 > $O/mb.txt 2>&1
 python3 tools/prof_summary.py $(find $O/p -name "*kernel_stats.csv") > $O/summary.txt
 A="--steps 2 --warmup 1 --cpu-sample 1 --latency-frames 0 --no-direct --no-stereo --no-undistort --no-c4 --no-a11"
-timeout -k 10 400 python bench.py $A > $O/bench.json 2> $O/bench.err
+timeout -k 10 400 python bench.py --full $A > $O/bench.json 2> $O/bench.err

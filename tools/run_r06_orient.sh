@@ -12,7 +12,7 @@ YGZFE_ORIENT16=1 YGZ_MB_STAGES=1 timeout -k 10 200 python tools/mb_fast.py 1024 
 YGZ_MB_STAGES=1 timeout -k 10 200 python tools/mb_fast.py 1024 $PWD/orb-ygz-slam_amd/lib/libygzfe_oe8.so > $O/mb32e8.txt 2>&1 || true
 A="--steps 10 --warmup 2 --cpu-sample 0 --latency-frames 0 --no-direct --no-stereo --no-bow --no-undistort --no-c4 --no-a11 --no-dropin"
 for r in 1 2; do
-timeout -k 10 300 python bench.py $A >> $O/o32.jsonl 2>> $O/err.log
-YGZFE_ORIENT16=1 timeout -k 10 300 python bench.py $A >> $O/o16.jsonl 2>> $O/err.log
-YGZFE_LIB=$PWD/orb-ygz-slam_amd/lib/libygzfe_oe8.so timeout -k 10 300 python bench.py $A >> $O/o32e8.jsonl 2>> $O/err.log
+timeout -k 10 300 python bench.py --full $A >> $O/o32.jsonl 2>> $O/err.log
+YGZFE_ORIENT16=1 timeout -k 10 300 python bench.py --full $A >> $O/o16.jsonl 2>> $O/err.log
+YGZFE_LIB=$PWD/orb-ygz-slam_amd/lib/libygzfe_oe8.so timeout -k 10 300 python bench.py --full $A >> $O/o32e8.jsonl 2>> $O/err.log
 done
