@@ -1070,6 +1070,9 @@ int ygzfe_batch_create(const ygzfe_orb_params *p, int device, int width, int hei
     const Plan &P = b->plan->hp();
     YGZ_TRY(b->pyr.ensure((size_t)max_frames * P.pyr_bytes));
     YGZ_TRY(b->ws.ensure(P, max_frames, P.kp_cap));
+    // the overflow flag ygzfe_batch_check reads: extraction clears it per call, but a batch that only
+    // matches / aligns bound buffers never extracts
+    YGZ_HIP(hipMemset(b->ws.err.p, 0, 16));
     YGZ_HIP(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
     for (int i = 0; i < 3; i++) {
         YGZ_HIP(hipStreamCreateWithFlags(&b->aux[i], hipStreamNonBlocking));

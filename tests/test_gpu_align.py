@@ -13,7 +13,10 @@ pytestmark = pytest.mark.gpu
 POSE_TOL = 1e-4
 
 
-def align_case(gpu, seed, n_usable_frac=1.0, max_level=3, min_level=1, motion_scale=1.0, method=0, nfeatures=None):
+def align_case(gpu, seed, n_usable_frac=1.0, max_level=3, min_level=1, motion_scale=1.0, method=0, nfeatures=None,
+               full=False):
+    """GPU and oracle results of one synthetic pair; with `full` also the oracle-side inputs
+    (tests/_align_cases.py's case record: pyramids, keypoints, map points, usable flags)."""
     sc = S.PlaneScene(seed)
     W, H, nf, sf, nl, ini, mn = S.CONFIGS["C2"]
     nf = nfeatures or nf
@@ -41,6 +44,10 @@ def align_case(gpu, seed, n_usable_frac=1.0, max_level=3, min_level=1, motion_sc
     ores = O.sparse_align(orc.pyramid(f_ref), orc.pyramid(f_cur), orc.inv_scale, ocam, kps, xyz, usable, max_level,
                           min_level, oT0, method=method)
     true_q, true_t = q_d, v
+    if full:
+        case = {"pyr_ref": orc.pyramid(f_ref), "pyr_cur": orc.pyramid(f_cur), "orc": orc, "ocam": ocam, "kps": kps,
+                "xyz": xyz, "usable": usable, "max_level": max_level, "min_level": min_level}
+        return res, ores, (true_q, true_t), case
     return res, ores, (true_q, true_t)
 
 

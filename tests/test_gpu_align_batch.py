@@ -18,7 +18,10 @@ POSE_TOL = 1e-4
 XI = np.array([0.012, -0.006, 0.009, 0.0025, -0.002, 0.0015], np.float32)
 
 
-def run_batch_align(gpu, F, stride, max_level, min_level, usable_frac=1.0, seed=11, nfeatures=None):
+def run_batch_align(gpu, F, stride, max_level, min_level, usable_frac=1.0, seed=11, nfeatures=None, full=False):
+    """Runs the batch and checks every pair's pose and n_visible against the oracle; with `full`
+    also returns the [P, 45] records (q, t, n_visible, chi2, H), the oracle's results and the
+    oracle-side inputs per pair (tests/_align_cases.py's case records)."""
     import torch
     W, H, nf, sf, nl, ini, mn = S.CONFIGS["C2"]
     nf = nfeatures or nf
@@ -57,15 +60,20 @@ def run_batch_align(gpu, F, stride, max_level, min_level, usable_frac=1.0, seed=
     ocam = O.Cam(*sc.cam)
     oT0 = O.se3_from((0, 0, 0, 1), (0, 0, 0))
     pyrs = [orc.pyramid(f) for f in frames]
-    errs = []
+    errs, ores, cases = [], [], []
     for p in range(P):
         n = len(kps[p])
         o = O.sparse_align(pyrs[p], pyrs[p + 1], orc.inv_scale, ocam, kps[p], xyz[p, :n], usable[p, :n], max_level,
                            min_level, oT0)
         err = S.se3_log_inf(res[p, 0:4], res[p, 4:7], np.array(o.T.q[:]), np.array(o.T.t[:]))
         errs.append(err)
+        ores.append(o)
+        cases.append({"pyr_ref": pyrs[p], "pyr_cur": pyrs[p + 1], "orc": orc, "ocam": ocam, "kps": kps[p],
+                      "xyz": xyz[p, :n], "usable": usable[p, :n], "max_level": max_level, "min_level": min_level})
         assert err <= POSE_TOL, f"pair {p}: GPU vs CPU pose differ by {err}"
         assert nvis[p] == o.n_visible, f"pair {p}: n_visible {nvis[p]} vs {o.n_visible}"
+    if full:
+        return np.array(errs), nvis, res, ores, cases
     return np.array(errs), nvis
 
 
