@@ -440,6 +440,104 @@ int ygzfe_search_local_points_direct(const ygzfe_frame *const *ref, int n_ref, c
                                      int cache_hit_th, float *px_out, int32_t *matched_item, int32_t *status,
                                      int *cache_success, int *local_ran);
 
+/* A keyframe's mvKeys, resident with its frame (they never change once the
+ * keyframe is made): uploaded once, read by ygzfe_search_local_map_direct.
+ * Every octave must lie inside the frame's pyramid (YGZFE_EINVAL otherwise; the
+ * earlier keypoints, if any, are kept).  n = 0 is a valid, empty table.  The
+ * keypoints belong to the frame's image: computing or uploading a pyramid into
+ * the frame (ygzfe_compute_pyramid*, ygzfe_frame_set_level(s)) drops them, and
+ * the buffer is freed with the frame.  The keyframes of a
+ * ygzfe_search_local_map_direct call must come from the current frame's
+ * extractor (calls on one extractor are serialised). */
+int ygzfe_frame_set_keypoints(ygzfe_frame *f, const ygzfe_kp *kps, int n);
+/* The number of keypoints set, or -1 when none were. */
+int ygzfe_frame_keypoint_count(const ygzfe_frame *f);
+
+/* Tracking::SearchLocalPointsDirect (Tracking.cc:2258-2410) from the raw local
+ * map: Frame::isInFrustum (Frame.cc:363-422), SelectNearestKeyframe
+ * (Tracking.cc:2412-2432), T_ref * P_w, the item list, the item search and the
+ * replay of ygzfe_search_local_points_direct all run on the device, in one call
+ * (one upload, one download, nothing returns to the host in between).
+ *
+ * View: the current frame's mRcw (row-major) / mtcw, mOw, the image bounds
+ * mnMinX..mnMaxY, the viewing-cosine limit (0.5 at both call sites) and mbf.
+ * Keyframe table, n_kf rows: ref[k] a frame of the current frame's size with
+ * keypoints set; kf_id[k] = mnId (unique); kf_excluded[k] = isBad() or
+ * == mpLastKeyFrame; T_rw[12k] = GetPose() as R row-major (9) then t (3);
+ * T_cr[k] = T_cur * T_ref^-1.
+ * Candidates, n_cache + n_local rows, cache rows first, each in the reference's
+ * iteration order: world / normal (3 floats each), min_dist / max_dist = the raw
+ * mfMinDistance / mfMaxDistance, skip = isBad() or a local point already in the
+ * cache; observations in CSR form, obs_kf a table row, obs_kp an index into that
+ * keyframe's keypoints, in any order, all of them.
+ *
+ * Arithmetic (float32, every operation rounded once, no fused multiply-add):
+ *   Pc_i = ((R[i][0]*P0 + R[i][1]*P1) + R[i][2]*P2) + t_i;   cull if Pc_z < 0
+ *   invz = 1 / Pc_z;  u = ((fx*Pc_x)*invz) + cx;  v = ((fy*Pc_y)*invz) + cy
+ *   cull if u < min_x || u > max_x;  cull if v < min_y || v > max_y
+ *   PO = P - Ow;  dist = sqrt((PO0*PO0 + PO1*PO1) + PO2*PO2)
+ *   cull if dist < 0.8f*min_dist || dist > 1.2f*max_dist
+ *   view_cos = ((PO0*n0 + PO1*n1) + PO2*n2) / dist;   cull if view_cos < limit
+ *   proj = (u, v, u - mbf*invz)
+ * The comparisons reject, so a NaN passes them as in the reference.  One
+ * deviation: a candidate whose u, v, dist or view_cos is not finite is culled
+ * (the reference would index its coverage grid with it; e.g. P == Ow with
+ * Pc = 0 passes every reference test with NaN).  Culling happens before
+ * anything touches an image.
+ * A candidate in view keeps the n_sel (1..YGZFE_DIRECT_MAX_SEL; 5 at the call
+ * sites) observations of largest kf_id among the keyframes not excluded, in
+ * descending kf_id order.  Each is one item: pt_ref_i = ((R_rw[i][0]*P0 +
+ * R_rw[i][1]*P1) + R_rw[i][2]*P2) + t_rw_i, kp_ref = the keyframe's keypoint
+ * obs_kp, T_cr of its row, px_proj = (u, v).
+ * From there the call equals ygzfe_search_local_points_direct over the
+ * candidates in view, in order (border, grid_size, cache_hit_th as there), and
+ * the result is mapped back to candidate rows.  A candidate in view without an
+ * eligible observation is FAILED, as in the reference.
+ *
+ * Outputs per candidate (each pointer may be NULL): status (the four codes
+ * above, or YGZFE_DIRECT_CULLED for a skipped or out-of-frustum candidate),
+ * px_out[2], matched_kf (table row, or -1), matched_kp (or -1), and what
+ * isInFrustum writes into the MapPoint: proj[3] (mTrackProjX, mTrackProjY,
+ * mTrackProjXR), view_cos, dist -- defined only where status != CULLED.
+ * PredictScale is left to the caller (from dist): the direct path never reads
+ * it, and a device log would not match the host's at level boundaries. */
+#define YGZFE_DIRECT_CULLED 4
+#define YGZFE_DIRECT_MAX_SEL 8
+typedef struct ygzfe_direct_view {
+    float R[9], t[3];   /* T_cw */
+    float Ow[3];
+    float min_x, max_x, min_y, max_y;
+    float view_cos_limit;
+    float mbf;
+} ygzfe_direct_view;
+typedef struct ygzfe_direct_keyframes {
+    int32_t n_kf;
+    const ygzfe_frame *const *ref;
+    const int64_t *kf_id;
+    const uint8_t *kf_excluded;
+    const float *T_rw;          /* [n_kf][12] */
+    const ygzfe_se3 *T_cr;
+} ygzfe_direct_keyframes;
+typedef struct ygzfe_direct_candidates {
+    int32_t n_cache, n_local;
+    const float *world, *normal;         /* [3n] */
+    const float *min_dist, *max_dist;    /* [n] */
+    const uint8_t *skip;                 /* [n] */
+    const int32_t *obs_ptr;              /* [n + 1] */
+    const int32_t *obs_kf, *obs_kp;      /* [obs_ptr[n]] */
+} ygzfe_direct_candidates;
+typedef struct ygzfe_direct_map_result {
+    int32_t *status;                     /* [n] */
+    float *px_out;                       /* [2n] */
+    int32_t *matched_kf, *matched_kp;    /* [n] */
+    float *proj;                         /* [3n] */
+    float *view_cos, *dist;              /* [n] */
+} ygzfe_direct_map_result;
+int ygzfe_search_local_map_direct(const ygzfe_frame *cur, const ygzfe_camera *cam, const ygzfe_direct_view *view,
+                                  const ygzfe_direct_keyframes *kfs, const ygzfe_direct_candidates *cand, int n_sel,
+                                  float border, int grid_size, int cache_hit_th,
+                                  const ygzfe_direct_map_result *out, int *cache_success, int *local_ran);
+
 /* ------------------------------------------------------------------------ */
 /* Stereo (Frame.cc:509-700)                                                 */
 /* Frame::ComputeStereoMatches (Frame.cc:509-682): left / right frames (their

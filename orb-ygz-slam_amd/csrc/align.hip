@@ -15,6 +15,10 @@
 //  * k_find_direct: FindDirectProjection (ORBmatcher.cc:1573-1602) =
 //    GetWarpAffineMatrix + GetBestSearchLevel + WarpAffine + Align2D, one lane
 //    per (map point, keyframe) item.
+//  * k_direct_setup / k_direct_scan_fill / k_direct_finish: the set-up of
+//    SearchLocalPointsDirect from the raw local map (Frame::isInFrustum,
+//    SelectNearestKeyframe, the CSR item list) around the item search and
+//    k_direct_replay, for ygzfe_search_local_map_direct.
 #include "kernels.hpp"
 
 namespace ygzfe {
@@ -1862,12 +1866,12 @@ hipError_t launch_find_direct(const uint8_t *const *ref_pyrs, const AlignLevels 
 // inside the 20 px border (Tracking.cc:2287-2296 / 2356-2364): the same answer
 // the reference's sequential loop with its `break` gives.
 
-__global__ __launch_bounds__(64 * kDirectWaves) void k_direct_items(
-    const uint8_t *const *__restrict__ ref_pyrs, AlignLevels lv, const uint8_t *__restrict__ cur_pyr, int nlevels,
-    const float *__restrict__ scale, float inv_sigma2_1, ygzfe_camera cam, int n,
+// item i of the call by one wave (the body of both item kernels)
+__device__ __forceinline__ void direct_item_wave(
+    const uint8_t *const *__restrict__ ref_pyrs, const AlignLevels &lv, const uint8_t *__restrict__ cur_pyr,
+    int nlevels, const float *__restrict__ scale, float inv_sigma2_1, const ygzfe_camera &cam, int n,
     const DirectItem *__restrict__ items, const ygzfe_se3 *__restrict__ tcr_tab, const float *__restrict__ px_proj,
-    float *__restrict__ px_out, uint8_t *__restrict__ ok_out) {
-    __shared__ DirectLds s[kDirectWaves];
+    float *__restrict__ px_out, uint8_t *__restrict__ ok_out, DirectLds *s) {
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int i = blockIdx.x * kDirectWaves + wave;
     if (i >= n) return;
@@ -1882,6 +1886,28 @@ __global__ __launch_bounds__(64 * kDirectWaves) void k_direct_items(
         px_out[2 * i + 1] = px[1];
         ok_out[i] = (uint8_t)ok;
     }
+}
+
+__global__ __launch_bounds__(64 * kDirectWaves) void k_direct_items(
+    const uint8_t *const *__restrict__ ref_pyrs, AlignLevels lv, const uint8_t *__restrict__ cur_pyr, int nlevels,
+    const float *__restrict__ scale, float inv_sigma2_1, ygzfe_camera cam, int n,
+    const DirectItem *__restrict__ items, const ygzfe_se3 *__restrict__ tcr_tab, const float *__restrict__ px_proj,
+    float *__restrict__ px_out, uint8_t *__restrict__ ok_out) {
+    __shared__ DirectLds s[kDirectWaves];
+    direct_item_wave(ref_pyrs, lv, cur_pyr, nlevels, scale, inv_sigma2_1, cam, n, items, tcr_tab, px_proj, px_out,
+                     ok_out, s);
+}
+
+// The same with the item count in device memory (written by k_direct_scan_fill of
+// this call): the grid covers the host's upper bound, waves past *n_items exit at once.
+__global__ __launch_bounds__(64 * kDirectWaves) void k_direct_items_counted(
+    const uint8_t *const *__restrict__ ref_pyrs, AlignLevels lv, const uint8_t *__restrict__ cur_pyr, int nlevels,
+    const float *__restrict__ scale, float inv_sigma2_1, ygzfe_camera cam, const int32_t *__restrict__ n_items,
+    const DirectItem *__restrict__ items, const ygzfe_se3 *__restrict__ tcr_tab, const float *__restrict__ px_proj,
+    float *__restrict__ px_out, uint8_t *__restrict__ ok_out) {
+    __shared__ DirectLds s[kDirectWaves];
+    direct_item_wave(ref_pyrs, lv, cur_pyr, nlevels, scale, inv_sigma2_1, cam, scalar_load(n_items), items, tcr_tab,
+                     px_proj, px_out, ok_out, s);
 }
 
 // Tracking::SearchLocalPointsDirect's sequential part (Tracking.cc:2258-2410) in one
@@ -2084,6 +2110,202 @@ hipError_t launch_search_direct(const uint8_t *const *ref_pyrs, const AlignLevel
                        px_proj, border, lv.w[0], lv.h[0], grid_size, grid_cols, ncell, cache_hit_th, px_out, matched,
                        status, hdr);
     (void)n_points;
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ local-map set-up on the device
+// ygzfe_search_local_map_direct: Frame::isInFrustum (Frame.cc:363-422) and
+// SelectNearestKeyframe (Tracking.cc:2412-2432) per candidate, T_ref * P_w per item.
+// The arithmetic is the one stated in include/ygzfe.h: float32, one rounding per
+// operation, no fused multiply-add.
+
+// ((R[i][0] * P0 + R[i][1] * P1) + R[i][2] * P2) + t_i
+__device__ __forceinline__ void rt_act(const float *R, const float *t, const float P[3], float o[3]) {
+    for (int i = 0; i < 3; i++)
+        o[i] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(R[3 * i], P[0]), __fmul_rn(R[3 * i + 1], P[1])),
+                                   __fmul_rn(R[3 * i + 2], P[2])),
+                         t[i]);
+}
+
+// sum of one int per thread over a workgroup of kDirectSetupThreads; s: 4 ints of LDS
+__device__ __forceinline__ int setup_block_sum(int x, int *s) {
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
+    __syncthreads();  // s may still be read from the last use
+    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = x;
+    __syncthreads();
+    return s[0] + s[1] + s[2] + s[3];
+}
+
+// One lane per candidate: the frustum test, then the n_sel eligible observations of
+// largest kf_id kept as a sorted list in registers (one insertion per observation).
+__global__ __launch_bounds__(kDirectSetupThreads) void k_direct_setup(int n, ygzfe_direct_view V, ygzfe_camera cam,
+                                                                      int n_sel, DirectMapDev in, DirectMapWork w) {
+    __shared__ int s_sum[4];
+    const int i = blockIdx.x * kDirectSetupThreads + threadIdx.x;
+    int c = 0;
+    if (i < n) {
+        bool cull = in.skip[i] != 0;
+        float u = 0.f, v = 0.f, ur = 0.f, vc = 0.f, dist = 0.f;
+        if (!cull) {
+            const float P[3] = {in.world[3 * i], in.world[3 * i + 1], in.world[3 * i + 2]};
+            float Pc[3];
+            rt_act(V.R, V.t, P, Pc);
+            cull = true;
+            if (!(Pc[2] < 0.0f)) {
+                const float invz = __fdiv_rn(1.0f, Pc[2]);
+                u = __fadd_rn(__fmul_rn(__fmul_rn(cam.fx, Pc[0]), invz), cam.cx);
+                v = __fadd_rn(__fmul_rn(__fmul_rn(cam.fy, Pc[1]), invz), cam.cy);
+                if (!(u < V.min_x || u > V.max_x) && !(v < V.min_y || v > V.max_y)) {
+                    const float PO[3] = {__fsub_rn(P[0], V.Ow[0]), __fsub_rn(P[1], V.Ow[1]), __fsub_rn(P[2], V.Ow[2])};
+                    // sqrtf, not __fsqrt_rn: the HIP header maps the latter to the native square root
+                    // (not correctly rounded); sqrtf is IEEE under the default
+                    // -fhip-fp32-correctly-rounded-divide-sqrt
+                    dist = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(PO[0], PO[0]), __fmul_rn(PO[1], PO[1])),
+                                           __fmul_rn(PO[2], PO[2])));
+                    if (!(dist < __fmul_rn(0.8f, in.min_dist[i]) || dist > __fmul_rn(1.2f, in.max_dist[i]))) {
+                        const float dot = __fadd_rn(__fadd_rn(__fmul_rn(PO[0], in.normal[3 * i]),
+                                                              __fmul_rn(PO[1], in.normal[3 * i + 1])),
+                                                    __fmul_rn(PO[2], in.normal[3 * i + 2]));
+                        vc = __fdiv_rn(dot, dist);
+                        // the stated deviation: a non-finite value is culled before it reaches the grid
+                        if (!(vc < V.view_cos_limit) && isfinite(u) && isfinite(v) && isfinite(dist) && isfinite(vc)) {
+                            cull = false;
+                            ur = __fsub_rn(u, __fmul_rn(V.mbf, invz));
+                        }
+                    }
+                }
+            }
+        }
+        int64_t ids[kDirectMaxSel];
+        int sk[kDirectMaxSel], sp[kDirectMaxSel];
+#pragma unroll
+        for (int j = 0; j < kDirectMaxSel; j++) {
+            ids[j] = 0;
+            sk[j] = -1;
+            sp[j] = -1;
+        }
+        if (!cull) {
+            for (int k = in.obs_ptr[i]; k < in.obs_ptr[i + 1]; k++) {
+                int s = in.obs_kf[k];
+                if (in.kf_excluded[s]) continue;
+                int64_t id = in.kf_id[s];
+                int q = in.obs_kp[k];
+                // insertion into the descending list; the displaced entry moves on
+#pragma unroll
+                for (int j = 0; j < kDirectMaxSel; j++) {
+                    if (j < n_sel && s >= 0 && (sk[j] < 0 || id > ids[j])) {
+                        const int64_t tid_ = ids[j];
+                        const int ts = sk[j], tp = sp[j];
+                        ids[j] = id;
+                        sk[j] = s;
+                        sp[j] = q;
+                        id = tid_;
+                        s = ts;
+                        q = tp;
+                    }
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < kDirectMaxSel; j++) c += sk[j] >= 0;
+        }
+#pragma unroll
+        for (int j = 0; j < kDirectMaxSel; j++) {
+            w.sel_kf[(size_t)i * kDirectMaxSel + j] = sk[j];
+            w.sel_kp[(size_t)i * kDirectMaxSel + j] = sp[j];
+        }
+        w.culled[i] = cull ? 1 : 0;
+        w.cnt[i] = c;
+        w.px_proj[2 * i] = cull ? 0.f : u;  // a culled row stays as a point without items: cell 0, never marked
+        w.px_proj[2 * i + 1] = cull ? 0.f : v;
+        w.proj[3 * i] = cull ? 0.f : u;
+        w.proj[3 * i + 1] = cull ? 0.f : v;
+        w.proj[3 * i + 2] = cull ? 0.f : ur;
+        w.view_cos[i] = cull ? 0.f : vc;
+        w.dist[i] = cull ? 0.f : dist;
+    }
+    const int total = setup_block_sum(c, s_sum);
+    if (threadIdx.x == 0) w.bsum[blockIdx.x] = total;
+}
+
+// Exclusive scan of the item counts into item_ptr and the item fill, in CSR order.
+// Workgroup b starts at the sum of bsum[0, b) (written by the launch before: no
+// communication between workgroups of this launch), then scans its 256 counts with
+// wave shuffles and one LDS step.  The last candidate's lane leaves item_ptr[n] and
+// *n_items.  Item j of candidate i: the keyframe slot is also its T_cr table entry.
+__global__ __launch_bounds__(kDirectSetupThreads) void k_direct_scan_fill(int n, DirectMapDev in, DirectMapWork w) {
+    __shared__ int s_sum[4], s_wave[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int i = blockIdx.x * kDirectSetupThreads + tid;
+    int part = 0;
+    for (int b = tid; b < (int)blockIdx.x; b += kDirectSetupThreads) part += w.bsum[b];
+    const int base = setup_block_sum(part, s_sum);
+    const int c = i < n ? w.cnt[i] : 0;
+    int x = c;  // inclusive scan over the wave
+    for (int off = 1; off < 64; off <<= 1) {
+        const int y = __shfl_up(x, off);
+        if (lane >= off) x += y;
+    }
+    if (lane == 63) s_wave[wave] = x;
+    __syncthreads();
+    int first = base + x - c;
+    for (int k = 0; k < wave; k++) first += s_wave[k];
+    if (i >= n) return;
+    w.item_ptr[i] = first;
+    if (i == n - 1) {
+        w.item_ptr[n] = first + c;
+        *w.n_items = first + c;
+    }
+    if (c == 0) return;
+    const float P[3] = {in.world[3 * i], in.world[3 * i + 1], in.world[3 * i + 2]};
+    DirectItem *items = (DirectItem *)w.items;
+    for (int j = 0; j < c; j++) {
+        const int s = w.sel_kf[(size_t)i * kDirectMaxSel + j], q = w.sel_kp[(size_t)i * kDirectMaxSel + j];
+        DirectItem it;
+        it.kp = in.kf_kps[s][q];
+        rt_act(in.T_rw + 12 * s, in.T_rw + 12 * s + 9, P, it.pt);
+        it.ref = s;
+        it.point = i;
+        it.tcr = s;
+        items[first + j] = it;
+    }
+}
+
+// matched item -> (keyframe slot, keypoint index); CULLED over the replay's status
+__global__ __launch_bounds__(kDirectSetupThreads) void k_direct_finish(int n, DirectMapWork w) {
+    const int i = blockIdx.x * kDirectSetupThreads + threadIdx.x;
+    if (i >= n) return;
+    const int m = w.matched_item[i];
+    int kf = -1, kp = -1;
+    if (m >= 0) {
+        const int j = m - w.item_ptr[i];
+        kf = w.sel_kf[(size_t)i * kDirectMaxSel + j];
+        kp = w.sel_kp[(size_t)i * kDirectMaxSel + j];
+    }
+    w.matched_kf[i] = kf;
+    w.matched_kp[i] = kp;
+    if (w.culled[i]) w.status[i] = YGZFE_DIRECT_CULLED;
+}
+
+hipError_t launch_search_local_map(const uint8_t *const *ref_pyrs, const AlignLevels &lv, const uint8_t *cur_pyr,
+                                   int nlevels, const float *scale, float inv_sigma2_1, const ygzfe_camera &cam,
+                                   const ygzfe_direct_view &view, int n_cache, int n_local, int n_sel, int max_items,
+                                   const DirectMapDev &in, const ygzfe_se3 *tcr_tab, const DirectMapWork &w,
+                                   float border, int grid_size, int cache_hit_th, hipStream_t st) {
+    const int n = n_cache + n_local;
+    if (n <= 0) return hipSuccess;
+    const dim3 blocks((n + kDirectSetupThreads - 1) / kDirectSetupThreads), threads(kDirectSetupThreads);
+    hipLaunchKernelGGL(k_direct_setup, blocks, threads, 0, st, n, view, cam, n_sel, in, w);
+    hipLaunchKernelGGL(k_direct_scan_fill, blocks, threads, 0, st, n, in, w);
+    if (max_items > 0)
+        hipLaunchKernelGGL(k_direct_items_counted, dim3((max_items + kDirectWaves - 1) / kDirectWaves),
+                           dim3(64 * kDirectWaves), 0, st, ref_pyrs, lv, cur_pyr, nlevels, scale, inv_sigma2_1, cam,
+                           w.n_items, (const DirectItem *)w.items, tcr_tab, w.px_proj, w.px_item, w.ok_item);
+    const int grid_cols = lv.w[0] / grid_size, ncell = (lv.h[0] / grid_size) * grid_cols;
+    const size_t lds = (size_t)((ncell + 31) / 32) * 4 + 4;
+    hipLaunchKernelGGL(k_direct_replay, dim3(1), dim3(1024), lds, st, n_cache, n_local, w.item_ptr, w.px_item,
+                       w.ok_item, w.px_proj, border, lv.w[0], lv.h[0], grid_size, grid_cols, ncell, cache_hit_th,
+                       w.px_out, w.matched_item, w.status, w.hdr);
+    hipLaunchKernelGGL(k_direct_finish, blocks, threads, 0, st, n, w);
     return hipGetLastError();
 }
 

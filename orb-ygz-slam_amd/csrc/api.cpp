@@ -415,6 +415,9 @@ struct ygzfe_frame {
     PlanDev *plan = nullptr;
     int W = 0, H = 0;
     DevBuf pyr;
+    // a keyframe's mvKeys (ygzfe_frame_set_keypoints), read by ygzfe_search_local_map_direct
+    DevBuf kps;
+    int n_kps = -1;
     // the captured single-frame extraction (ygzfe_extract, no existing rows)
     hipGraph_t graph = nullptr;
     hipGraphExec_t gexec = nullptr;
@@ -671,6 +674,7 @@ int ygzfe_compute_pyramid(ygzfe_extractor *ex, ygzfe_frame *f, const uint8_t *im
     if (!ex || !f || !img || stride < f->W) { set_error("invalid argument"); return YGZFE_EINVAL; }
     YGZ_TRY(ensure_device(ex->device));
     std::lock_guard<std::mutex> lk(ex->mu);
+    f->n_kps = -1;  // keypoints belong to the image they were set for
     // the image is copied into pinned staging (the caller may reuse `img` at once)
     // and DMA'd from there; everything that reads the pyramid is ordered after it
     // on ex->stream or synchronises first (ygzfe_frame_level), so no
@@ -696,6 +700,7 @@ int ygzfe_compute_pyramid_device(ygzfe_extractor *ex, ygzfe_frame *f, const uint
                                  void *stream) {
     if (!ex || !f || !d_img || stride < f->W) { set_error("invalid argument"); return YGZFE_EINVAL; }
     YGZ_TRY(ensure_device(ex->device));
+    f->n_kps = -1;
     hipStream_t st = stream ? (hipStream_t)stream : ex->stream;
     YGZ_TRY(ex->order_after_align(st));
     YGZ_HIP(hipMemcpy2DAsync(f->pyr.p, f->W, d_img, stride, f->W, f->H, hipMemcpyDeviceToDevice, st));
@@ -740,6 +745,7 @@ int ygzfe_frame_set_level(ygzfe_frame *f, int level, const uint8_t *src, int src
     const LevelDesc &L = P.lv[level];
     if (src_stride < L.w) { set_error("src_stride < level width"); return YGZFE_EINVAL; }
     ygzfe_extractor *ex = f->ex;
+    f->n_kps = -1;
     YGZ_TRY(ensure_device(ex->device));
     std::lock_guard<std::mutex> lk(ex->mu);
     YGZ_HIP(hipStreamSynchronize(ex->stream));  // the staging's previous use
@@ -806,6 +812,7 @@ int ygzfe_frame_set_levels(ygzfe_frame *f, int first, int count, const uint8_t *
     const Plan &P = f->plan->hp();
     for (int i = 0; i < count; i++)
         if (!src[i] || src_stride[i] < P.lv[first + i].w) { set_error("level %d: no buffer or stride < width", first + i); return YGZFE_EINVAL; }
+    f->n_kps = -1;
     ygzfe_extractor *ex = f->ex;
     YGZ_TRY(ensure_device(ex->device));
     std::lock_guard<std::mutex> lk(ex->mu);
@@ -2074,6 +2081,197 @@ extern "C" int ygzfe_search_local_points_direct(const ygzfe_frame *const *ref, i
     return search_direct_impl(ref, n_ref, cur, cam, n_cache, n_local, item_ptr, ref_index, kp_ref, pt_ref, T_cr,
                               px_proj, border, grid_size, cache_hit_th, px_out, matched_item, status, cache_success,
                               local_ran);
+}
+
+// ------------------------------------------------------------------ local map, set up on the device
+extern "C" int ygzfe_frame_set_keypoints(ygzfe_frame *f, const ygzfe_kp *kps, int n) {
+    if (!f || n < 0 || (n > 0 && !kps)) { set_error("invalid argument"); return YGZFE_EINVAL; }
+    const Plan &P = f->plan->hp();
+    for (int i = 0; i < n; i++)
+        if (kps[i].octave < 0 || kps[i].octave >= P.nlevels) {
+            set_error("kps[%d].octave %d out of range", i, kps[i].octave);
+            return YGZFE_EINVAL;
+        }
+    ygzfe_extractor *ex = f->ex;
+    YGZ_TRY(ensure_device(ex->device));
+    std::lock_guard<std::mutex> lk(ex->mu);
+    YGZ_HIP(hipStreamSynchronize(ex->stream));  // no call in flight reads the old table
+    YGZ_TRY(f->kps.ensure(sizeof(ygzfe_kp) * (size_t)std::max(1, n)));
+    if (n > 0) {
+        YGZ_HIP(hipMemcpyAsync(f->kps.p, kps, sizeof(ygzfe_kp) * (size_t)n, hipMemcpyHostToDevice, ex->stream));
+        YGZ_HIP(hipStreamSynchronize(ex->stream));
+    }
+    f->n_kps = n;
+    return YGZFE_OK;
+}
+
+extern "C" int ygzfe_frame_keypoint_count(const ygzfe_frame *f) { return f ? f->n_kps : -1; }
+
+// One packed H2D (tables, candidates, observations), k_direct_setup + k_direct_scan_fill +
+// the counted item search + k_direct_replay + k_direct_finish, one packed D2H: the call
+// shape of search_direct_impl, with the item list built on the device.
+extern "C" int ygzfe_search_local_map_direct(const ygzfe_frame *cur, const ygzfe_camera *cam,
+                                             const ygzfe_direct_view *view, const ygzfe_direct_keyframes *kfs,
+                                             const ygzfe_direct_candidates *cand, int n_sel, float border,
+                                             int grid_size, int cache_hit_th, const ygzfe_direct_map_result *out,
+                                             int *cache_success, int *local_ran) {
+    if (!cur || !cam || !view || !kfs || !cand || !out || cand->n_cache < 0 || cand->n_local < 0 || kfs->n_kf < 0) {
+        set_error("invalid argument");
+        return YGZFE_EINVAL;
+    }
+    const int n_kf = kfs->n_kf, n = cand->n_cache + cand->n_local;
+    if (n_kf > 0 && (!kfs->ref || !kfs->kf_id || !kfs->kf_excluded || !kfs->T_rw || !kfs->T_cr)) {
+        set_error("null keyframe table");
+        return YGZFE_EINVAL;
+    }
+    if (n > 0 && (!cand->world || !cand->normal || !cand->min_dist || !cand->max_dist || !cand->skip || !cand->obs_ptr)) {
+        set_error("null candidate array");
+        return YGZFE_EINVAL;
+    }
+    if (n_sel < 1 || n_sel > YGZFE_DIRECT_MAX_SEL) {
+        set_error("n_sel %d outside [1, %d]", n_sel, YGZFE_DIRECT_MAX_SEL);
+        return YGZFE_EINVAL;
+    }
+    if (grid_size <= 0) { set_error("grid_size must be positive"); return YGZFE_EINVAL; }
+    const Plan &P = cur->plan->hp();
+    const long ncell = (long)(P.lv[0].h / grid_size) * (P.lv[0].w / grid_size);
+    if (ncell > kDirectMaxGridCells) {
+        set_error("coverage grid of %ld cells exceeds %d", ncell, kDirectMaxGridCells);
+        return YGZFE_EINVAL;
+    }
+    if (n == 0) {
+        if (cache_success) *cache_success = 0;
+        if (local_ran) *local_ran = !(0 > cache_hit_th);
+        return YGZFE_OK;
+    }
+    for (int k = 0; k < n_kf; k++)
+        if (!kfs->ref[k] || kfs->ref[k]->ex != cur->ex || kfs->ref[k]->plan != cur->plan || kfs->ref[k]->n_kps < 0) {
+            set_error("keyframe %d missing, of another extractor or size, or without keypoints", k);
+            return YGZFE_EINVAL;
+        }
+    const int32_t *op = cand->obs_ptr;
+    if (op[0] != 0) { set_error("obs_ptr[0] must be 0"); return YGZFE_EINVAL; }
+    long max_items_l = 0;
+    for (int i = 0; i < n; i++) {
+        if (op[i + 1] < op[i]) { set_error("obs_ptr not monotone at %d", i); return YGZFE_EINVAL; }
+        max_items_l += std::min(op[i + 1] - op[i], n_sel);
+    }
+    const int n_obs = op[n];
+    if (n_obs > 0 && (!cand->obs_kf || !cand->obs_kp)) { set_error("null observation array"); return YGZFE_EINVAL; }
+    for (int k = 0; k < n_obs; k++) {
+        const int s = cand->obs_kf[k];
+        if (s < 0 || s >= n_kf) { set_error("obs_kf[%d] out of range", k); return YGZFE_EINVAL; }
+        if (cand->obs_kp[k] < 0 || cand->obs_kp[k] >= kfs->ref[s]->n_kps) {
+            set_error("obs_kp[%d] = %d outside keyframe %d's %d keypoints", k, cand->obs_kp[k], s, kfs->ref[s]->n_kps);
+            return YGZFE_EINVAL;
+        }
+    }
+    if (max_items_l > 0x7fffffff / (long)sizeof(DirectItem)) { set_error("too many items"); return YGZFE_EINVAL; }
+    const int max_items = (int)max_items_l;  // <= min(n_obs, n_sel * n)
+    ygzfe_extractor *ex = cur->ex;
+    YGZ_TRY(ensure_device(ex->device));
+    std::lock_guard<std::mutex> lk(ex->mu);
+    hipStream_t st = ex->stream;
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t nk = (size_t)std::max(1, n_kf), N = (size_t)n;
+    // in: [ref ptrs][kp ptrs][scale][kf_id][T_rw][T_cr][excluded] [world][normal][min][max][obs_ptr][skip] [obs_kf][obs_kp]
+    const size_t i_ref = 0, i_kpp = al(i_ref + 8 * nk), i_sc = al(i_kpp + 8 * nk), i_id = al(i_sc + 4 * kMaxLevels);
+    const size_t i_trw = al(i_id + 8 * nk), i_tcr = al(i_trw + 48 * nk), i_ex = al(i_tcr + sizeof(ygzfe_se3) * nk);
+    const size_t i_w = al(i_ex + nk), i_nr = al(i_w + 12 * N), i_mn = al(i_nr + 12 * N), i_mx = al(i_mn + 4 * N);
+    const size_t i_op = al(i_mx + 4 * N), i_sk = al(i_op + 4 * (N + 1)), i_ok = al(i_sk + N);
+    const size_t i_oq = al(i_ok + 4 * (size_t)n_obs), in_bytes = al(i_oq + 4 * (size_t)n_obs);
+    // back: [hdr][status][px_out][matched_kf][matched_kp][proj][view_cos][dist]
+    const size_t b_st = 16, b_px = b_st + 4 * N, b_mk = b_px + 8 * N, b_mp = b_mk + 4 * N, b_pj = b_mp + 4 * N;
+    const size_t b_vc = b_pj + 12 * N, b_ds = b_vc + 4 * N, back_bytes = b_ds + 4 * N;
+    // scratch: [culled][cnt][bsum][sel_kf][sel_kp][item_ptr][n_items][px_proj][matched_item][items][px_item][ok_item]
+    const size_t nblk = (N + kDirectSetupThreads - 1) / kDirectSetupThreads, M = (size_t)max_items;
+    const size_t s_cu = al(back_bytes), s_cn = al(s_cu + N), s_bs = al(s_cn + 4 * N), s_sf = al(s_bs + 4 * nblk);
+    const size_t s_sp = al(s_sf + 4 * kDirectMaxSel * N), s_ip = al(s_sp + 4 * kDirectMaxSel * N);
+    const size_t s_ni = al(s_ip + 4 * (N + 1)), s_pp = al(s_ni + 4), s_mi = al(s_pp + 8 * N), s_it = al(s_mi + 4 * N);
+    const size_t s_pi = al(s_it + sizeof(DirectItem) * M), s_oi = al(s_pi + 8 * M), out_bytes = al(s_oi + M);
+    YGZ_TRY(ex->direct_hin.ensure(in_bytes));
+    YGZ_TRY(ex->direct_hout.ensure(back_bytes));
+    YGZ_TRY(ex->direct_dev.ensure(in_bytes + out_bytes));
+    uint8_t *h = ex->direct_hin.as<uint8_t>(), *d = ex->direct_dev.as<uint8_t>(), *dout = d + in_bytes;
+    const uint8_t **ptrs = (const uint8_t **)(h + i_ref);
+    const ygzfe_kp **kpp = (const ygzfe_kp **)(h + i_kpp);
+    for (int k = 0; k < n_kf; k++) {
+        ptrs[k] = kfs->ref[k]->pyr.as<uint8_t>();
+        kpp[k] = kfs->ref[k]->kps.as<ygzfe_kp>();
+    }
+    float *sc = (float *)(h + i_sc);
+    for (int l = 0; l < P.nlevels; l++) sc[l] = P.lv[l].scale;
+    if (n_kf > 0) {
+        memcpy(h + i_id, kfs->kf_id, 8 * (size_t)n_kf);
+        memcpy(h + i_trw, kfs->T_rw, 48 * (size_t)n_kf);
+        memcpy(h + i_tcr, kfs->T_cr, sizeof(ygzfe_se3) * (size_t)n_kf);
+        memcpy(h + i_ex, kfs->kf_excluded, (size_t)n_kf);
+    }
+    memcpy(h + i_w, cand->world, 12 * N);
+    memcpy(h + i_nr, cand->normal, 12 * N);
+    memcpy(h + i_mn, cand->min_dist, 4 * N);
+    memcpy(h + i_mx, cand->max_dist, 4 * N);
+    memcpy(h + i_op, op, 4 * (N + 1));
+    memcpy(h + i_sk, cand->skip, N);
+    if (n_obs > 0) {
+        memcpy(h + i_ok, cand->obs_kf, 4 * (size_t)n_obs);
+        memcpy(h + i_oq, cand->obs_kp, 4 * (size_t)n_obs);
+    }
+    YGZ_HIP(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, st));
+    DirectMapDev in;
+    in.world = (const float *)(d + i_w);
+    in.normal = (const float *)(d + i_nr);
+    in.min_dist = (const float *)(d + i_mn);
+    in.max_dist = (const float *)(d + i_mx);
+    in.skip = d + i_sk;
+    in.obs_ptr = (const int32_t *)(d + i_op);
+    in.obs_kf = (const int32_t *)(d + i_ok);
+    in.obs_kp = (const int32_t *)(d + i_oq);
+    in.kf_id = (const int64_t *)(d + i_id);
+    in.kf_excluded = d + i_ex;
+    in.T_rw = (const float *)(d + i_trw);
+    in.kf_kps = (const ygzfe_kp *const *)(d + i_kpp);
+    DirectMapWork w;
+    w.culled = dout + s_cu;
+    w.cnt = (int32_t *)(dout + s_cn);
+    w.bsum = (int32_t *)(dout + s_bs);
+    w.sel_kf = (int32_t *)(dout + s_sf);
+    w.sel_kp = (int32_t *)(dout + s_sp);
+    w.item_ptr = (int32_t *)(dout + s_ip);
+    w.n_items = (int32_t *)(dout + s_ni);
+    w.items = dout + s_it;
+    w.px_proj = (float *)(dout + s_pp);
+    w.px_item = (float *)(dout + s_pi);
+    w.ok_item = dout + s_oi;
+    w.matched_item = (int32_t *)(dout + s_mi);
+    w.hdr = (int32_t *)dout;
+    w.status = (int32_t *)(dout + b_st);
+    w.px_out = (float *)(dout + b_px);
+    w.matched_kf = (int32_t *)(dout + b_mk);
+    w.matched_kp = (int32_t *)(dout + b_mp);
+    w.proj = (float *)(dout + b_pj);
+    w.view_cos = (float *)(dout + b_vc);
+    w.dist = (float *)(dout + b_ds);
+    YGZ_HIP(launch_search_local_map((const uint8_t *const *)(d + i_ref), levels_of(P), cur->pyr.as<uint8_t>(),
+                                    P.nlevels, (const float *)(d + i_sc),
+                                    ex->scales.inv_sigma2[1 < P.nlevels ? 1 : 0], *cam, *view, cand->n_cache,
+                                    cand->n_local, n_sel, max_items, in, (const ygzfe_se3 *)(d + i_tcr), w, border,
+                                    grid_size, cache_hit_th, st));
+    uint8_t *hb = ex->direct_hout.as<uint8_t>();
+    YGZ_HIP(hipMemcpyAsync(hb, dout, back_bytes, hipMemcpyDeviceToHost, st));
+    YGZ_HIP(hipStreamSynchronize(st));
+    if (out->status) memcpy(out->status, hb + b_st, 4 * N);
+    if (out->px_out) memcpy(out->px_out, hb + b_px, 8 * N);
+    if (out->matched_kf) memcpy(out->matched_kf, hb + b_mk, 4 * N);
+    if (out->matched_kp) memcpy(out->matched_kp, hb + b_mp, 4 * N);
+    if (out->proj) memcpy(out->proj, hb + b_pj, 12 * N);
+    if (out->view_cos) memcpy(out->view_cos, hb + b_vc, 4 * N);
+    if (out->dist) memcpy(out->dist, hb + b_ds, 4 * N);
+    int32_t hdr[2];
+    memcpy(hdr, hb, 8);
+    if (cache_success) *cache_success = hdr[0];
+    if (local_ran) *local_ran = hdr[1];
+    return YGZFE_OK;
 }
 
 // --------------------------------------------------------------------------

@@ -198,6 +198,48 @@ hipError_t launch_search_direct(const uint8_t *const *ref_pyrs, const AlignLevel
                                 hipStream_t st);
 constexpr int kDirectMaxGridCells = 65536 * 8 - 64;  // LDS bitmap of k_direct_replay (<= 64 KB)
 
+// ygzfe_search_local_map_direct: the raw local map of one call, in device memory
+constexpr int kDirectMaxSel = YGZFE_DIRECT_MAX_SEL;
+constexpr int kDirectSetupThreads = 256;  // candidates per workgroup of the set-up / scan kernels
+struct DirectMapDev {
+    // candidates [n]
+    const float *world, *normal, *min_dist, *max_dist;
+    const uint8_t *skip;
+    const int32_t *obs_ptr, *obs_kf, *obs_kp;
+    // keyframe table [n_kf]
+    const int64_t *kf_id;
+    const uint8_t *kf_excluded;
+    const float *T_rw;               // [n_kf][12]: R row-major, then t
+    const ygzfe_kp *const *kf_kps;   // the keyframes' resident keypoints
+};
+// set-up scratch and per-candidate results of the call, in device memory
+struct DirectMapWork {
+    uint8_t *culled;       // [n]
+    int32_t *cnt;          // [n] items of the candidate (0 when culled)
+    int32_t *bsum;         // [ceil(n / kDirectSetupThreads)] items per set-up workgroup
+    int32_t *sel_kf;       // [n][kDirectMaxSel] chosen keyframe slots, descending kf_id
+    int32_t *sel_kp;       // [n][kDirectMaxSel] their keypoint indices
+    int32_t *item_ptr;     // [n + 1]
+    int32_t *n_items;      // [1]
+    void *items;           // [upper bound] DirectItem
+    float *px_proj;        // [n][2] (u, v); (0, 0) when culled
+    float *px_item;        // [upper bound][2]
+    uint8_t *ok_item;      // [upper bound]
+    int32_t *matched_item; // [n] k_direct_replay's matched item
+    // results
+    int32_t *hdr, *status, *matched_kf, *matched_kp;
+    float *px_out, *proj, *view_cos, *dist;
+};
+// Frustum cull + keyframe choice + item list (k_direct_setup, k_direct_scan_fill), the
+// item search over *n_items, k_direct_replay over the candidate rows, and the mapping of
+// the result to (keyframe slot, keypoint) with CULLED rows (k_direct_finish).
+// tcr_tab: T_cr per keyframe slot.  max_items: the host's bound on the item count.
+hipError_t launch_search_local_map(const uint8_t *const *ref_pyrs, const AlignLevels &lv, const uint8_t *cur_pyr,
+                                   int nlevels, const float *scale, float inv_sigma2_1, const ygzfe_camera &cam,
+                                   const ygzfe_direct_view &view, int n_cache, int n_local, int n_sel, int max_items,
+                                   const DirectMapDev &in, const ygzfe_se3 *tcr_tab, const DirectMapWork &w,
+                                   float border, int grid_size, int cache_hit_th, hipStream_t st);
+
 // slots.hip: offline sequence mode result slots
 hipError_t launch_pack_slots(const ygzfe_kp *kps, const uint8_t *desc, const int *counts, int kp_cap,
                              const ygzfe_align_result *align, int frame_begin, int n_frames, int global_first,

@@ -153,6 +153,15 @@ class Frame:
         img = np.ascontiguousarray(img, np.uint8)
         _check(lib().ygzfe_frame_set_level(self.h, l, _p(img), img.shape[1]), "frame_set_level")
 
+    def set_keypoints(self, kps):
+        """A keyframe's mvKeys, resident with the frame (read by search_local_map_direct)."""
+        kps = np.ascontiguousarray(kps, KP_DTYPE)
+        _check(lib().ygzfe_frame_set_keypoints(self.h, _p(kps), len(kps)), "frame_set_keypoints")
+
+    def keypoint_count(self):
+        """Keypoints set with set_keypoints, or -1 when none were."""
+        return int(lib().ygzfe_frame_keypoint_count(self.h))
+
 
 class ORBextractor:
     """ORBextractor(nfeatures, scaleFactor, nlevels, iniThFAST, minThFAST) (ORBextractor.h:53-57)."""
@@ -663,6 +672,92 @@ def search_local_points_direct(ref_frames, cur_frame, cam, n_cache, item_ptr, re
                                                   C.byref(cs), C.byref(lr)),
            "search_local_points_direct")
     return px_out, matched, status, cs.value, bool(lr.value)
+
+
+DIRECT_CULLED = 4
+DIRECT_MAX_SEL = 8
+
+
+class DirectView(C.Structure):
+    """The current frame's side of Frame::isInFrustum: mRcw (row-major), mtcw, mOw, the image
+    bounds, the viewing-cosine limit and mbf."""
+    _fields_ = [("R", C.c_float * 9), ("t", C.c_float * 3), ("Ow", C.c_float * 3), ("min_x", C.c_float),
+                ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float), ("view_cos_limit", C.c_float),
+                ("mbf", C.c_float)]
+
+    @staticmethod
+    def make(R, t, Ow, bounds, view_cos_limit=0.5, mbf=0.0):
+        v = DirectView()
+        v.R[:] = [float(x) for x in np.asarray(R, np.float32).reshape(9)]
+        v.t[:] = [float(x) for x in np.asarray(t, np.float32).reshape(3)]
+        v.Ow[:] = [float(x) for x in np.asarray(Ow, np.float32).reshape(3)]
+        v.min_x, v.max_x, v.min_y, v.max_y = (float(np.float32(b)) for b in bounds)
+        v.view_cos_limit, v.mbf = float(np.float32(view_cos_limit)), float(np.float32(mbf))
+        return v
+
+
+class _DirectKeyframes(C.Structure):
+    _fields_ = [("n_kf", C.c_int32), ("ref", C.c_void_p), ("kf_id", C.c_void_p), ("kf_excluded", C.c_void_p),
+                ("T_rw", C.c_void_p), ("T_cr", C.c_void_p)]
+
+
+class _DirectCandidates(C.Structure):
+    _fields_ = [("n_cache", C.c_int32), ("n_local", C.c_int32), ("world", C.c_void_p), ("normal", C.c_void_p),
+                ("min_dist", C.c_void_p), ("max_dist", C.c_void_p), ("skip", C.c_void_p), ("obs_ptr", C.c_void_p),
+                ("obs_kf", C.c_void_p), ("obs_kp", C.c_void_p)]
+
+
+class _DirectMapResult(C.Structure):
+    _fields_ = [("status", C.c_void_p), ("px_out", C.c_void_p), ("matched_kf", C.c_void_p),
+                ("matched_kp", C.c_void_p), ("proj", C.c_void_p), ("view_cos", C.c_void_p), ("dist", C.c_void_p)]
+
+
+def search_local_map_direct(kf_frames, cur_frame, cam, view, kf_id, kf_excluded, T_rw, T_cr, n_cache, world, normal,
+                            min_dist, max_dist, skip, obs_ptr, obs_kf, obs_kp, n_sel=5, border=20.0, grid_size=5,
+                            cache_hit_th=150):
+    """Tracking::SearchLocalPointsDirect from the raw local map (ygzfe_search_local_map_direct): the
+    frustum cull, the choice of the n_sel keyframes of largest kf_id per point, T_ref * P_w, the item
+    search and the replay all on the device.  kf_frames: the keyframe table's frames, each with
+    set_keypoints() done; kf_id int64[n_kf], kf_excluded uint8[n_kf], T_rw float32[n_kf, 12] (R
+    row-major, t), T_cr SE3_DTYPE[n_kf].  Candidates (the first n_cache are the cache): world /
+    normal float32[n, 3], min_dist / max_dist float32[n], skip uint8[n], observations in CSR form
+    (obs_kf a table row, obs_kp a keypoint index of that keyframe).  Returns a dict of the
+    per-candidate arrays status (DIRECT_*), px_out, matched_kf, matched_kp, proj, view_cos, dist,
+    and (cache_success, local_ran)."""
+    n_kf = len(kf_frames)
+    refs = (C.c_void_p * max(1, n_kf))(*[f.h.value for f in kf_frames])
+    kf_id = np.ascontiguousarray(kf_id, np.int64)
+    kf_excluded = np.ascontiguousarray(kf_excluded, np.uint8)
+    T_rw = np.ascontiguousarray(T_rw, np.float32).reshape(-1, 12)
+    T_cr = np.ascontiguousarray(T_cr, SE3_DTYPE)
+    if not (len(kf_id) == len(kf_excluded) == len(T_rw) == len(T_cr) == n_kf):
+        raise YgzfeError("search_local_map_direct: keyframe table arrays differ in length")
+    world = np.ascontiguousarray(world, np.float32).reshape(-1, 3)
+    normal = np.ascontiguousarray(normal, np.float32).reshape(-1, 3)
+    min_dist = np.ascontiguousarray(min_dist, np.float32)
+    max_dist = np.ascontiguousarray(max_dist, np.float32)
+    skip = np.ascontiguousarray(skip, np.uint8)
+    obs_ptr = np.ascontiguousarray(obs_ptr, np.int32)
+    obs_kf = np.ascontiguousarray(obs_kf, np.int32)
+    obs_kp = np.ascontiguousarray(obs_kp, np.int32)
+    n = len(world)
+    if not (len(normal) == len(min_dist) == len(max_dist) == len(skip) == n and len(obs_ptr) == n + 1
+            and len(obs_kf) == len(obs_kp) and (n == 0 or len(obs_kf) >= obs_ptr.max())):
+        raise YgzfeError("search_local_map_direct: candidate arrays differ in length")
+    res = {"status": np.zeros(n, np.int32), "px_out": np.zeros((n, 2), np.float32),
+           "matched_kf": np.full(n, -1, np.int32), "matched_kp": np.full(n, -1, np.int32),
+           "proj": np.zeros((n, 3), np.float32), "view_cos": np.zeros(n, np.float32), "dist": np.zeros(n, np.float32)}
+    kfs = _DirectKeyframes(n_kf, C.cast(refs, C.c_void_p), _p(kf_id), _p(kf_excluded), _p(T_rw), _p(T_cr))
+    cand = _DirectCandidates(int(n_cache), n - int(n_cache), _p(world), _p(normal), _p(min_dist), _p(max_dist),
+                             _p(skip), _p(obs_ptr), _p(obs_kf), _p(obs_kp))
+    out = _DirectMapResult(*[_p(res[k]) for k in ("status", "px_out", "matched_kf", "matched_kp", "proj", "view_cos",
+                                                   "dist")])
+    cs, lr = C.c_int(), C.c_int()
+    _check(lib().ygzfe_search_local_map_direct(cur_frame.h, C.byref(cam), C.byref(view), C.byref(kfs), C.byref(cand),
+                                               int(n_sel), C.c_float(border), int(grid_size), int(cache_hit_th),
+                                               C.byref(out), C.byref(cs), C.byref(lr)),
+           "search_local_map_direct")
+    return res, cs.value, bool(lr.value)
 
 
 class Batch:
