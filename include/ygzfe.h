@@ -539,6 +539,53 @@ int ygzfe_search_local_map_direct(const ygzfe_frame *cur, const ygzfe_camera *ca
                                   const ygzfe_direct_map_result *out, int *cache_success, int *local_ran);
 
 /* ------------------------------------------------------------------------ */
+/* Pose-only optimisation (Optimizer.cc:1656-1842)                           */
+/* Optimizer::PoseOptimization(Frame*): one SE3 vertex, one unary reprojection
+ * edge per map point (EdgeSE3ProjectXYZOnlyPose where mvuRight < 0,
+ * EdgeStereoSE3ProjectXYZOnlyPose otherwise), 4 rounds of up to 10
+ * Levenberg-Marquardt iterations with the Huber kernel (dropped for the last
+ * round), each restarted from the input pose over the edges the previous
+ * round left inliers; FP64 like g2o.  The whole function is one launch, one
+ * workgroup per problem. */
+typedef struct ygzfe_pose_opt_result {
+    ygzfe_se3 T_cw;          /* SetPose(estimate.cast<float>()) (Optimizer.cc:1839) */
+    double q[4], t[3];       /* the same before the cast: quat (x,y,z,w) + t */
+    int32_t n_corr;          /* nInitialCorrespondences (Optimizer.cc:1667) */
+    int32_t n_inliers;       /* the return value, nInitialCorrespondences - nBad (:1841) */
+    int32_t rounds;          /* rounds run (1..4, 0 if n_corr < 3; -1: see the batch form) */
+    int32_t iters[4];        /* optimize() iterations per round (0 for a round with no inlier edge left) */
+    int32_t rejected[4];     /* rejected LM trials per round */
+    double chi2[4];          /* activeRobustChi2 at the end of each round's optimize */
+} ygzfe_pose_opt_result;
+
+/* Host pointers; one packed H2D, one launch, one D2H, one synchronisation.
+ * kps[n] = mvKeys (pt and octave are read), u_right = mvuRight (NULL: all
+ * mono; < 0: mono row), xw[3n] = GetWorldPos() per row, present[n] =
+ * (mvpMapPoints[i] != NULL), inv_level_sigma2[n_levels] = mvInvLevelSigma2.
+ * outlier_out[n] = mvbOutlier: written for present rows only, and not at all
+ * when n_corr < 3 (the call then returns 0 inliers and T_cw = T_cw_init).
+ * A present row's octave outside [0, n_levels) is YGZFE_EINVAL.  Non-finite
+ * inputs end in a normal return (every loop of the kernel is bounded). */
+int ygzfe_pose_optimization(int device, const ygzfe_camera *cam, float bf, const ygzfe_se3 *T_cw_init, int n,
+                            const ygzfe_kp *kps, const float *u_right, const float *xw, const uint8_t *present,
+                            const float *inv_level_sigma2, int n_levels, uint8_t *outlier_out,
+                            ygzfe_pose_opt_result *result);
+/* Many problems in one launch (a batch of frames, or Relocalization's candidate
+ * keyframes, Tracking.cc:2563-2640): every pointer is a DEVICE pointer, nothing
+ * synchronises.  Problem p owns edge rows [d_problem_ptr[p], d_problem_ptr[p+1])
+ * of the concatenated edge arrays and d_cam[p], d_bf[p], d_T_init[p],
+ * d_results[p]; d_u_right may be NULL.  d_outlier rows follow the rule above.
+ * A problem with a present row whose octave is out of range gets rounds = -1,
+ * n_inliers = 0, T_cw = T_init and no flag written (the host form rejects it
+ * before the launch).
+ * Results are bit-identical to the host form's and from run to run. */
+int ygzfe_pose_optimization_batch(int device, int n_problems, const int32_t *d_problem_ptr,
+                                  const ygzfe_camera *d_cam, const float *d_bf, const ygzfe_se3 *d_T_init,
+                                  const ygzfe_kp *d_kps, const float *d_u_right, const float *d_xw,
+                                  const uint8_t *d_present, const float *d_inv_level_sigma2, int n_levels,
+                                  uint8_t *d_outlier, ygzfe_pose_opt_result *d_results, void *stream);
+
+/* ------------------------------------------------------------------------ */
 /* Stereo (Frame.cc:509-700)                                                 */
 /* Frame::ComputeStereoMatches (Frame.cc:509-682): left / right frames (their
  * ORBextractor pyramids, mvImagePyramid), mvKeys + mDescriptors (nl) and

@@ -3371,3 +3371,82 @@ extern "C" int ygzfe_search_by_bow(ygzfe_match_frame *kf, ygzfe_match_frame *F, 
     *nmatches = c.nmatches;
     return YGZFE_OK;
 }
+
+// ------------------------------------------------------------------ pose-only optimisation
+// Optimizer::PoseOptimization (Optimizer.cc:1656-1842), poseopt.hip
+int ygzfe_pose_optimization_batch(int device, int n_problems, const int32_t *d_problem_ptr,
+                                  const ygzfe_camera *d_cam, const float *d_bf, const ygzfe_se3 *d_T_init,
+                                  const ygzfe_kp *d_kps, const float *d_u_right, const float *d_xw,
+                                  const uint8_t *d_present, const float *d_inv_level_sigma2, int n_levels,
+                                  uint8_t *d_outlier, ygzfe_pose_opt_result *d_results, void *stream) {
+    if (n_problems < 0 || n_levels <= 0 ||
+        (n_problems > 0 && (!d_problem_ptr || !d_cam || !d_bf || !d_T_init || !d_kps || !d_xw || !d_present ||
+                            !d_inv_level_sigma2 || !d_outlier || !d_results))) {
+        set_error("invalid argument");
+        return YGZFE_EINVAL;
+    }
+    if (n_problems == 0) return YGZFE_OK;
+    YGZ_TRY(ensure_device(device));
+    YGZ_HIP(launch_pose_opt(n_problems, d_problem_ptr, d_cam, d_bf, d_T_init, d_kps, d_u_right, d_xw, d_present,
+                            d_inv_level_sigma2, n_levels, d_outlier, d_results, (hipStream_t)stream));
+    return YGZFE_OK;
+}
+
+int ygzfe_pose_optimization(int device, const ygzfe_camera *cam, float bf, const ygzfe_se3 *T_cw_init, int n,
+                            const ygzfe_kp *kps, const float *u_right, const float *xw, const uint8_t *present,
+                            const float *inv_level_sigma2, int n_levels, uint8_t *outlier_out,
+                            ygzfe_pose_opt_result *result) {
+    if (!cam || !T_cw_init || !result || n < 0 || n_levels <= 0 || !inv_level_sigma2 ||
+        (n > 0 && (!kps || !xw || !present || !outlier_out))) {
+        set_error("invalid argument");
+        return YGZFE_EINVAL;
+    }
+    for (int i = 0; i < n; i++)
+        if (present[i] && (kps[i].octave < 0 || kps[i].octave >= n_levels)) {
+            set_error("row %d: octave %d outside [0, %d)", i, kps[i].octave, n_levels);
+            return YGZFE_EINVAL;
+        }
+    YGZ_TRY(ensure_device(device));
+    StagingLease S;
+    YGZ_TRY(S.acquire(device));
+    // in: [problem_ptr 2][cam][bf][T_init][inv_sigma2][kps][xw][u_right][present]  out: [result][outlier]
+    const size_t rows = (size_t)(n > 0 ? n : 1);
+    const size_t o_cam = 16, o_bf = o_cam + 16, o_T = o_bf + 16, o_sig = o_T + 32;
+    const size_t o_kps = o_sig + align16((size_t)n_levels * 4), o_xw = o_kps + align16(rows * sizeof(ygzfe_kp));
+    const size_t o_ur = o_xw + align16(rows * 12), o_pr = o_ur + align16(rows * 4);
+    const size_t in_bytes = o_pr + align16(rows);
+    const size_t o_flags = align16(sizeof(ygzfe_pose_opt_result)), out_bytes = o_flags + align16(rows);
+    YGZ_TRY(S->hin.ensure(in_bytes));
+    YGZ_TRY(S->hout.ensure(out_bytes));
+    YGZ_TRY(S->dev.ensure(in_bytes + out_bytes));
+    uint8_t *h = S->hin.as<uint8_t>(), *d = S->dev.as<uint8_t>();
+    const int32_t ptr[2] = {0, n};
+    memcpy(h, ptr, sizeof(ptr));
+    memcpy(h + o_cam, cam, sizeof(*cam));
+    memcpy(h + o_bf, &bf, sizeof(bf));
+    memcpy(h + o_T, T_cw_init, sizeof(*T_cw_init));
+    memcpy(h + o_sig, inv_level_sigma2, (size_t)n_levels * 4);
+    if (n > 0) {
+        memcpy(h + o_kps, kps, (size_t)n * sizeof(ygzfe_kp));
+        memcpy(h + o_xw, xw, (size_t)n * 12);
+        if (u_right) memcpy(h + o_ur, u_right, (size_t)n * 4);
+        memcpy(h + o_pr, present, (size_t)n);
+    }
+    YGZ_HIP(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, S->stream));
+    uint8_t *dout = d + in_bytes;
+    YGZ_TRY(ygzfe_pose_optimization_batch(
+        device, 1, reinterpret_cast<const int32_t *>(d), reinterpret_cast<const ygzfe_camera *>(d + o_cam),
+        reinterpret_cast<const float *>(d + o_bf), reinterpret_cast<const ygzfe_se3 *>(d + o_T),
+        reinterpret_cast<const ygzfe_kp *>(d + o_kps), u_right ? reinterpret_cast<const float *>(d + o_ur) : nullptr,
+        reinterpret_cast<const float *>(d + o_xw), d + o_pr, reinterpret_cast<const float *>(d + o_sig), n_levels,
+        dout + o_flags, reinterpret_cast<ygzfe_pose_opt_result *>(dout), S->stream));
+    YGZ_HIP(hipMemcpyAsync(S->hout.p, dout, out_bytes, hipMemcpyDeviceToHost, S->stream));
+    YGZ_HIP(hipStreamSynchronize(S->stream));
+    memcpy(result, S->hout.p, sizeof(*result));
+    if (result->rounds > 0) {  // mvbOutlier is written where a map point is present only
+        const uint8_t *flags = S->hout.as<uint8_t>() + o_flags;
+        for (int i = 0; i < n; i++)
+            if (present[i]) outlier_out[i] = flags[i];
+    }
+    return YGZFE_OK;
+}

@@ -256,4 +256,10 @@ hipError_t launch_remap_linear(const uint8_t *src, size_t src_pitch, int W, int 
                                const uint16_t *map2, const void *boxes, int max_box, bool any_large, uint8_t *dst,
                                size_t dst_pitch, int dstride, int n_images, hipStream_t st);
 
+// poseopt.hip: Optimizer::PoseOptimization, one workgroup per problem (CSR over edge rows); device pointers
+hipError_t launch_pose_opt(int n_problems, const int32_t *ptr, const ygzfe_camera *cam, const float *bf,
+                           const ygzfe_se3 *T_init, const ygzfe_kp *kps, const float *u_right, const float *xw,
+                           const uint8_t *present, const float *inv_sigma2, int n_levels, uint8_t *outlier,
+                           ygzfe_pose_opt_result *res, hipStream_t st);
+
 }  // namespace ygzfe

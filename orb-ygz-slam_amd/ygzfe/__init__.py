@@ -978,3 +978,76 @@ def plane_points_device(d_kps, cap, n_frames, cam, d_r3, d_cz, plane_z, d_xyz, s
                                       C.c_void_p(d_cz), C.c_float(plane_z), C.c_void_p(d_xyz), C.c_void_p(stream))
     if rc != 0:
         raise YgzfeError("plane_points launch failed")
+
+
+# ------------------------------------------------------------------ pose-only optimisation
+class PoseOptResult(C.Structure):
+    """ygzfe_pose_opt_result (Optimizer::PoseOptimization, Optimizer.cc:1656-1842)."""
+    _fields_ = [("T_cw", SE3), ("q", C.c_double * 4), ("t", C.c_double * 3), ("n_corr", C.c_int32),
+                ("n_inliers", C.c_int32), ("rounds", C.c_int32), ("iters", C.c_int32 * 4),
+                ("rejected", C.c_int32 * 4), ("chi2", C.c_double * 4)]
+
+
+POSE_OPT_RESULT_DTYPE = np.dtype({"names": ["Tq", "Tt", "q", "t", "n_corr", "n_inliers", "rounds", "iters", "rejected",
+                                            "chi2"],
+                                  "formats": [("<f4", 4), ("<f4", 3), ("<f8", 4), ("<f8", 3), "<i4", "<i4", "<i4",
+                                              ("<i4", 4), ("<i4", 4), ("<f8", 4)],
+                                  "offsets": [0, 16, 32, 64, 88, 92, 96, 100, 116, 136], "itemsize": 168})
+assert C.sizeof(PoseOptResult) == POSE_OPT_RESULT_DTYPE.itemsize
+
+
+def pose_optimization(cam, bf, T_cw_init, kps, xw, present, inv_level_sigma2, u_right=None, outlier=None, device=0):
+    """Optimizer::PoseOptimization(Frame*) on the device.  kps: KP_DTYPE rows (mvKeys), xw [n,3] world
+    points, present [n] (mvpMapPoints[i] != NULL), u_right: mvuRight or None (all mono), outlier: the
+    caller's mvbOutlier (rows without a map point keep their value; default zeros).
+    -> (PoseOptResult, outlier uint8 [n])."""
+    kps = np.ascontiguousarray(kps, KP_DTYPE)
+    n = len(kps)
+    xw = np.ascontiguousarray(xw, np.float32).reshape(n, 3)
+    pr = np.ascontiguousarray(present, np.uint8)
+    sig = np.ascontiguousarray(inv_level_sigma2, np.float32)
+    ur = None if u_right is None else np.ascontiguousarray(u_right, np.float32)
+    out = np.zeros(n, np.uint8) if outlier is None else np.array(outlier, np.uint8)
+    if len(pr) != n or len(out) != n or (ur is not None and len(ur) != n):
+        raise YgzfeError("pose_optimization: array lengths differ")
+    res = PoseOptResult()
+    _check(lib().ygzfe_pose_optimization(device, C.byref(cam), C.c_float(bf), C.byref(T_cw_init), n, _p(kps),
+                                         None if ur is None else _p(ur), _p(xw), _p(pr), _p(sig), len(sig), _p(out),
+                                         C.byref(res)), "pose_optimization")
+    return res, out
+
+
+def pose_optimization_batch(problem_ptr, cam, bf, T_init, kps, u_right, xw, present, inv_level_sigma2, outlier,
+                            results=None, device=0):
+    """Many PoseOptimization problems in one launch on torch.cuda.current_stream(); every argument is a
+    torch device tensor (u_right may be None) and nothing synchronises.  problem_ptr: int32 [P+1] CSR
+    over the edge rows; cam: float32 [P,4]; bf: float32 [P]; T_init: float32 [P,7] (q xyzw, t); kps: uint8
+    [n,28] (KP_DTYPE bytes); xw: float32 [n,3]; present, outlier: uint8 [n]; inv_level_sigma2: float32
+    [n_levels].  outlier is written in place; -> results, uint8 [P, 168] (view with POSE_OPT_RESULT_DTYPE)."""
+    import torch
+    P = int(problem_ptr.numel()) - 1
+    tensors = [problem_ptr, cam, bf, T_init, kps, xw, present, inv_level_sigma2, outlier] + \
+        ([] if u_right is None else [u_right])
+    for t in tensors:
+        if not t.is_cuda or not t.is_contiguous():
+            raise YgzfeError("pose_optimization_batch takes contiguous device tensors")
+    want = [(problem_ptr, torch.int32), (cam, torch.float32), (bf, torch.float32), (T_init, torch.float32),
+            (kps, torch.uint8), (xw, torch.float32), (present, torch.uint8), (inv_level_sigma2, torch.float32),
+            (outlier, torch.uint8)] + ([] if u_right is None else [(u_right, torch.float32)])
+    if any(t.dtype != d for t, d in want):
+        raise YgzfeError("pose_optimization_batch: wrong tensor dtype")
+    n = int(present.numel())
+    if (P < 0 or cam.numel() != 4 * P or bf.numel() != P or T_init.numel() != 7 * P or kps.numel() != 28 * n or
+            xw.numel() != 3 * n or outlier.numel() != n or (u_right is not None and u_right.numel() != n)):
+        raise YgzfeError("pose_optimization_batch: tensor shapes differ")
+    if results is None:
+        results = torch.zeros((max(P, 0), POSE_OPT_RESULT_DTYPE.itemsize), dtype=torch.uint8, device=present.device)
+    elif results.numel() != P * POSE_OPT_RESULT_DTYPE.itemsize or results.dtype != torch.uint8:
+        raise YgzfeError("pose_optimization_batch: results must be uint8 [P, 168]")
+    vp = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    stream = torch.cuda.current_stream(present.device).cuda_stream
+    _check(lib().ygzfe_pose_optimization_batch(device, P, vp(problem_ptr), vp(cam), vp(bf), vp(T_init), vp(kps),
+                                               None if u_right is None else vp(u_right), vp(xw), vp(present),
+                                               vp(inv_level_sigma2), int(inv_level_sigma2.numel()), vp(outlier),
+                                               vp(results), C.c_void_p(stream)), "pose_optimization_batch")
+    return results
