@@ -20,6 +20,7 @@
 
 #include "kernels.hpp"
 #include "plan.hpp"
+#include "staging.hpp"
 
 namespace ygzfe {
 
@@ -151,6 +152,12 @@ struct HostBuf {
 
 static inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
+#define YGZ_TRY(x)                          \
+    do {                                    \
+        int r_ = (x);                       \
+        if (r_ != YGZFE_OK) return r_;      \
+    } while (0)
+
 // Host entry points without a handle (Hamming, RGB-D depth lookup, Align2D on a host
 // image, FAST-10 ROIs): a call leases a staging area from a process-wide pool per
 // device -- its own non-blocking stream, a device buffer and pinned in / out buffers
@@ -187,6 +194,7 @@ struct StagingLease {
     }
     CallStaging *operator->() const { return s; }
     int acquire(int dev) {
+        YGZ_TRY(ensure_device(dev));
         device = dev;
         {
             std::lock_guard<std::mutex> lk(staging_mutex());
@@ -206,13 +214,23 @@ struct StagingLease {
         s = n;
         return YGZFE_OK;
     }
+    // a packed call of `in` bytes up and `out` bytes back, on the device [in][out]: reserve(), fill hin,
+    // upload(), the launches, download() into hout
+    int reserve(size_t in, size_t out) {
+        YGZ_TRY(s->hin.ensure(in));
+        YGZ_TRY(s->hout.ensure(out));
+        return s->dev.ensure(in + out);
+    }
+    int upload(size_t in) {
+        YGZ_HIP(hipMemcpyAsync(s->dev.p, s->hin.p, in, hipMemcpyHostToDevice, s->stream));
+        return YGZFE_OK;
+    }
+    int download(size_t in, size_t out) {
+        YGZ_HIP(hipMemcpyAsync(s->hout.p, at<uint8_t>(s->dev.p, in), out, hipMemcpyDeviceToHost, s->stream));
+        YGZ_HIP(hipStreamSynchronize(s->stream));
+        return YGZFE_OK;
+    }
 };
-
-#define YGZ_TRY(x)                          \
-    do {                                    \
-        int r_ = (x);                       \
-        if (r_ != YGZFE_OK) return r_;      \
-    } while (0)
 
 struct PlanDev {
     PlanHost host;
@@ -1440,23 +1458,19 @@ int ygzfe_hamming_best2(int device, const uint8_t *query, int nq, const uint8_t 
         return YGZFE_EINVAL;
     }
     if (nq == 0) return YGZFE_OK;
-    YGZ_TRY(ensure_device(device));
     StagingLease S;
     YGZ_TRY(S.acquire(device));
-    // in: [query][train]  out: [best_idx][best_dist][second_dist]
-    const size_t o_t = align16((size_t)nq * 32), in_bytes = o_t + align16((size_t)(nt > 0 ? nt : 1) * 32);
+    BlockLayout in{16};  // in: [query][train]  out: [best_idx][best_dist][second_dist]
+    const size_t o_q = in.take(nq, 32), o_t = in.take(nt > 0 ? nt : 1, 32), in_bytes = in.size();
     const size_t out_bytes = (size_t)nq * 12;
-    YGZ_TRY(S->hin.ensure(in_bytes));
-    YGZ_TRY(S->hout.ensure(out_bytes));
-    YGZ_TRY(S->dev.ensure(in_bytes + out_bytes));
+    YGZ_TRY(S.reserve(in_bytes, out_bytes));
     uint8_t *h = S->hin.as<uint8_t>(), *d = S->dev.as<uint8_t>();
-    memcpy(h, query, (size_t)nq * 32);
+    memcpy(h + o_q, query, (size_t)nq * 32);
     if (nt > 0) memcpy(h + o_t, train, (size_t)nt * 32);
-    YGZ_HIP(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, S->stream));
-    int32_t *bi = reinterpret_cast<int32_t *>(d + in_bytes), *bd = bi + nq, *sd = bd + nq;
-    YGZ_HIP(launch_hamming_best2(d, nq, d + o_t, nt, bi, bd, sd, S->stream));
-    YGZ_HIP(hipMemcpyAsync(S->hout.p, bi, out_bytes, hipMemcpyDeviceToHost, S->stream));
-    YGZ_HIP(hipStreamSynchronize(S->stream));
+    YGZ_TRY(S.upload(in_bytes));
+    int32_t *bi = at<int32_t>(d, in_bytes), *bd = bi + nq, *sd = bd + nq;
+    YGZ_HIP(launch_hamming_best2(d + o_q, nq, d + o_t, nt, bi, bd, sd, S->stream));
+    YGZ_TRY(S.download(in_bytes, out_bytes));
     const int32_t *ho = S->hout.as<int32_t>();
     memcpy(best_idx, ho, (size_t)nq * 4);
     memcpy(best_dist, ho + nq, (size_t)nq * 4);
@@ -1473,27 +1487,21 @@ int ygzfe_hamming_csr(int device, const uint8_t *query, int nq, const uint8_t *t
     if (!query || !train || !cand || !dist_out) { set_error("invalid argument"); return YGZFE_EINVAL; }
     for (int k = 0; k < nc; k++)
         if (cand[k] < 0 || cand[k] >= nt) { set_error("candidate index %d out of range", cand[k]); return YGZFE_EINVAL; }
-    YGZ_TRY(ensure_device(device));
     StagingLease S;
     YGZ_TRY(S.acquire(device));
-    // in: [query][train][row_ptr][cand]  out: [dist]
-    const size_t o_t = align16((size_t)nq * 32), o_r = o_t + align16((size_t)nt * 32);
-    const size_t o_c = o_r + align16((size_t)(nq + 1) * 4), in_bytes = o_c + align16((size_t)nc * 4);
-    const size_t out_bytes = (size_t)nc * 4;
-    YGZ_TRY(S->hin.ensure(in_bytes));
-    YGZ_TRY(S->hout.ensure(out_bytes));
-    YGZ_TRY(S->dev.ensure(in_bytes + out_bytes));
+    BlockLayout in{16};  // in: [query][train][row_ptr][cand]  out: [dist]
+    const size_t o_q = in.take(nq, 32), o_t = in.take(nt, 32), o_r = in.take((size_t)nq + 1, 4), o_c = in.take(nc, 4);
+    const size_t in_bytes = in.size(), out_bytes = (size_t)nc * 4;
+    YGZ_TRY(S.reserve(in_bytes, out_bytes));
     uint8_t *h = S->hin.as<uint8_t>(), *d = S->dev.as<uint8_t>();
-    memcpy(h, query, (size_t)nq * 32);
+    memcpy(h + o_q, query, (size_t)nq * 32);
     memcpy(h + o_t, train, (size_t)nt * 32);
     memcpy(h + o_r, row_ptr, (size_t)(nq + 1) * 4);
     memcpy(h + o_c, cand, (size_t)nc * 4);
-    YGZ_HIP(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, S->stream));
-    int32_t *ds = reinterpret_cast<int32_t *>(d + in_bytes);
-    YGZ_HIP(launch_hamming_csr(d, nq, d + o_t, reinterpret_cast<const int32_t *>(d + o_r),
-                               reinterpret_cast<const int32_t *>(d + o_c), ds, S->stream));
-    YGZ_HIP(hipMemcpyAsync(S->hout.p, ds, out_bytes, hipMemcpyDeviceToHost, S->stream));
-    YGZ_HIP(hipStreamSynchronize(S->stream));
+    YGZ_TRY(S.upload(in_bytes));
+    YGZ_HIP(launch_hamming_csr(d + o_q, nq, d + o_t, at<const int32_t>(d, o_r), at<const int32_t>(d, o_c),
+                               at<int32_t>(d, in_bytes), S->stream));
+    YGZ_TRY(S.download(in_bytes, out_bytes));
     memcpy(dist_out, S->hout.p, out_bytes);
     return YGZFE_OK;
 }
@@ -1574,9 +1582,9 @@ static int sparse_align_begin(const ygzfe_frame *ref, const ygzfe_frame *cur, co
     n = n_use;
     // one packed H2D from pinned staging: [job][keypoints][xyz][usable] (16-B aligned
     // pieces), cached device buffers, one D2H of the result
-    const size_t o_k = align16(sizeof(AlignJob)), o_x = o_k + align16(sizeof(ygzfe_kp) * (size_t)n);
-    const size_t o_u = o_x + align16(sizeof(float) * 3 * (size_t)n), in_bytes = o_u + align16((size_t)n);
-    const size_t spj = sparse_align_scratch_floats(n);
+    BlockLayout in{16};
+    const size_t o_job = in.take(sizeof(AlignJob)), o_k = in.take(n, sizeof(ygzfe_kp)), o_x = in.take(n, 12);
+    const size_t o_u = in.take(n), in_bytes = in.size(), spj = sparse_align_scratch_floats(n);
     YGZ_TRY(ex->align_in.ensure(in_bytes));
     YGZ_TRY(ex->align_scratch.ensure(sizeof(float) * spj));
     YGZ_TRY(ex->align_out.ensure(sizeof(ygzfe_align_result)));
@@ -1585,22 +1593,22 @@ static int sparse_align_begin(const ygzfe_frame *ref, const ygzfe_frame *cur, co
     AlignJob job;
     job.ref_pyr = ref->pyr.as<uint8_t>();
     job.cur_pyr = cur->pyr.as<uint8_t>();
-    job.kps = reinterpret_cast<const ygzfe_kp *>(din + o_k);
-    job.xyz = reinterpret_cast<const float *>(din + o_x);
+    job.kps = at<const ygzfe_kp>(din, o_k);
+    job.xyz = at<const float>(din, o_x);
     job.usable = din + o_u;
     job.n = n;
     job.max_level = max_level;
     job.min_level = min_level;
     job.method = method;
     job.T_init = *T_init;
-    memcpy(hin, &job, sizeof(job));
+    memcpy(hin + o_job, &job, sizeof(job));
     if (n == n_all) {
         memcpy(hin + o_k, kps, sizeof(ygzfe_kp) * (size_t)n);
         memcpy(hin + o_x, xyz_ref, sizeof(float) * 3 * (size_t)n);
         memcpy(hin + o_u, usable, (size_t)n);
     } else {
-        ygzfe_kp *hk = reinterpret_cast<ygzfe_kp *>(hin + o_k);
-        float *hx = reinterpret_cast<float *>(hin + o_x);
+        ygzfe_kp *hk = at<ygzfe_kp>(hin, o_k);
+        float *hx = at<float>(hin, o_x);
         for (int i = 0, j = 0; i < n_all; i++)
             if (usable[i]) {
                 hk[j] = kps[i];
@@ -1610,9 +1618,8 @@ static int sparse_align_begin(const ygzfe_frame *ref, const ygzfe_frame *cur, co
         memset(hin + o_u, 1, (size_t)n);
     }
     YGZ_HIP(hipMemcpyAsync(din, hin, in_bytes, hipMemcpyHostToDevice, st));
-    YGZ_HIP(launch_sparse_align(levels_of(P), *cam, reinterpret_cast<const AlignJob *>(din), 1,
-                                ex->align_scratch.as<float>(), spj, ex->align_out.as<ygzfe_align_result>(), st, n,
-                                method));
+    YGZ_HIP(launch_sparse_align(levels_of(P), *cam, at<const AlignJob>(din, o_job), 1, ex->align_scratch.as<float>(),
+                                spj, ex->align_out.as<ygzfe_align_result>(), st, n, method));
     YGZ_HIP(hipMemcpyAsync(ex->ahout.p, ex->align_out.p, sizeof(ygzfe_align_result), hipMemcpyDeviceToHost, st));
     YGZ_HIP(hipEventRecord(ex->ev_align_done, st));
     ex->align_pending = true;
@@ -1730,22 +1737,22 @@ extern "C" int ygzfe_align2d_batch(const ygzfe_frame *cur, int level, int n, con
     YGZ_TRY(ensure_device(ex->device));
     std::lock_guard<std::mutex> lk(ex->mu);
     hipStream_t st = ex->stream;
-    // in: [patches with border][patches][px]  out: [px][converged]
-    const size_t o_p = align16((size_t)n * 100), o_x = o_p + align16((size_t)n * 64), in_bytes = o_x + align16((size_t)n * 8);
-    const size_t out_bytes = (size_t)n * 9;
+    BlockLayout in{16}, out{16};  // in: [patches with border][patches][px]  out: [px][converged]
+    const size_t o_b = in.take(n, 100), o_p = in.take(n, 64), o_x = in.take(n, 8), in_bytes = in.size();
+    const size_t o_px = out.take(n, 9), out_bytes = out.end();  // px and converged, packed
     YGZ_TRY(ex->direct_hin.ensure(in_bytes));
     YGZ_TRY(ex->direct_hout.ensure(out_bytes));
-    YGZ_TRY(ex->direct_dev.ensure(in_bytes + align16(out_bytes)));
+    YGZ_TRY(ex->direct_dev.ensure(in_bytes + out.size()));
     uint8_t *h = ex->direct_hin.as<uint8_t>(), *d = ex->direct_dev.as<uint8_t>();
-    memcpy(h, patches_with_border, (size_t)n * 100);
+    memcpy(h + o_b, patches_with_border, (size_t)n * 100);
     memcpy(h + o_p, patches, (size_t)n * 64);
     memcpy(h + o_x, px_io, (size_t)n * 8);
     YGZ_HIP(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, st));
-    float *dpx = reinterpret_cast<float *>(d + in_bytes);
-    uint8_t *dconv = d + in_bytes + (size_t)n * 8;
+    float *dpx = at<float>(d, in_bytes + o_px);
+    uint8_t *dconv = d + in_bytes + o_px + (size_t)n * 8;
     YGZ_HIP(hipMemcpyAsync(dpx, d + o_x, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
     const LevelDesc &L = P.lv[level];
-    YGZ_HIP(launch_align2d(cur->pyr.as<uint8_t>() + L.off, L.w, L.h, n, d, d + o_p, n_iter, dpx, dconv, st));
+    YGZ_HIP(launch_align2d(cur->pyr.as<uint8_t>() + L.off, L.w, L.h, n, d + o_b, d + o_p, n_iter, dpx, dconv, st));
     YGZ_HIP(hipMemcpyAsync(ex->direct_hout.p, dpx, out_bytes, hipMemcpyDeviceToHost, st));
     YGZ_HIP(hipStreamSynchronize(st));
     memcpy(px_io, ex->direct_hout.p, (size_t)n * 8);
@@ -1777,27 +1784,21 @@ extern "C" int ygzfe_fast10_detect(int device, const uint8_t *img, int width, in
         }
     }
     if (n_roi == 0) return YGZFE_OK;
-    YGZ_TRY(ensure_device(device));
     StagingLease S;
     YGZ_TRY(S.acquire(device));
-    // in: [image][rois]  out: [counts][xy]
-    const size_t img_b = (size_t)stride * height, o_r = align16(img_b), in_bytes = o_r + align16((size_t)n_roi * 16);
-    const size_t o_xy = align16((size_t)n_roi * 4), out_bytes = o_xy + (size_t)n_roi * cap * 4;
-    YGZ_TRY(S->hin.ensure(in_bytes));
-    YGZ_TRY(S->hout.ensure(out_bytes));
-    YGZ_TRY(S->dev.ensure(in_bytes + out_bytes));
+    BlockLayout in{16}, out{16};  // in: [image][rois]  out: [counts][xy]
+    const size_t o_img = in.take((size_t)stride * height), o_r = in.take(n_roi, 16), in_bytes = in.size();
+    const size_t o_cnt = out.take(n_roi, 4), o_xy = out.take((size_t)n_roi * cap, 4), out_bytes = out.end();
+    YGZ_TRY(S.reserve(in_bytes, out_bytes));
     uint8_t *h = S->hin.as<uint8_t>(), *d = S->dev.as<uint8_t>();
     // the caller's last row may hold only `width` bytes (a cv::Mat ROI view)
-    memcpy(h, img, (size_t)(height - 1) * stride + width);
+    memcpy(h + o_img, img, (size_t)(height - 1) * stride + width);
     memcpy(h + o_r, rois, (size_t)n_roi * 16);
-    YGZ_HIP(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, S->stream));
-    int32_t *dc = reinterpret_cast<int32_t *>(d + in_bytes);
-    int16_t *dxy = reinterpret_cast<int16_t *>(d + in_bytes + o_xy);
-    YGZ_HIP(launch_fast10_rois(d, stride, reinterpret_cast<const int *>(d + o_r), n_roi, barrier, variant, dxy, cap,
-                               dc, S->stream));
-    YGZ_HIP(hipMemcpyAsync(S->hout.p, dc, out_bytes, hipMemcpyDeviceToHost, S->stream));
-    YGZ_HIP(hipStreamSynchronize(S->stream));
-    memcpy(counts, S->hout.p, (size_t)n_roi * 4);
+    YGZ_TRY(S.upload(in_bytes));
+    YGZ_HIP(launch_fast10_rois(d + o_img, stride, at<const int>(d, o_r), n_roi, barrier, variant,
+                               at<int16_t>(d, in_bytes + o_xy), cap, at<int32_t>(d, in_bytes + o_cnt), S->stream));
+    YGZ_TRY(S.download(in_bytes, out_bytes));
+    memcpy(counts, S->hout.as<uint8_t>() + o_cnt, (size_t)n_roi * 4);
     if (cap > 0) memcpy(xy, S->hout.as<uint8_t>() + o_xy, (size_t)n_roi * cap * 4);
     for (int r = 0; r < n_roi; r++)
         if (counts[r] > cap) {
@@ -1814,18 +1815,18 @@ extern "C" int ygzfe_debug_dso_cells(int device, const uint8_t *img, int width, 
         return YGZFE_EINVAL;
     }
     const size_t ncells = (size_t)(height / g) * (width / g), img_b = (size_t)width * height;
-    const size_t o_f = align16(img_b), fb = ncells * g * g;
+    BlockLayout blk{16};  // device block: [image][flags]
+    const size_t fb = ncells * g * g, o_img = blk.take(img_b), o_f = blk.take(fb);
     if (ncells == 0) return YGZFE_OK;
-    YGZ_TRY(ensure_device(device));
     StagingLease S;
     YGZ_TRY(S.acquire(device));
-    YGZ_TRY(S->hin.ensure(img_b));
+    YGZ_TRY(S->hin.ensure(img_b));  // not the lease's frame: the image goes up without its padding
     YGZ_TRY(S->hout.ensure(fb));
-    YGZ_TRY(S->dev.ensure(o_f + fb));
+    YGZ_TRY(S->dev.ensure(blk.end()));
     uint8_t *d = S->dev.as<uint8_t>();
     memcpy(S->hin.p, img, img_b);
-    YGZ_HIP(hipMemcpyAsync(d, S->hin.p, img_b, hipMemcpyHostToDevice, S->stream));
-    YGZ_HIP(launch_dso_cells_debug(d, width, height, g, barrier, d + o_f, S->stream));
+    YGZ_HIP(hipMemcpyAsync(d + o_img, S->hin.p, img_b, hipMemcpyHostToDevice, S->stream));
+    YGZ_HIP(launch_dso_cells_debug(d + o_img, width, height, g, barrier, d + o_f, S->stream));
     YGZ_HIP(hipMemcpyAsync(S->hout.p, d + o_f, fb, hipMemcpyDeviceToHost, S->stream));
     YGZ_HIP(hipStreamSynchronize(S->stream));
     memcpy(flags, S->hout.p, fb);
@@ -1841,10 +1842,10 @@ extern "C" int ygzfe_align2d_image(int device, const uint8_t *img, int w, int h,
         set_error("invalid argument");
         return YGZFE_EINVAL;
     }
-    YGZ_TRY(ensure_device(device));
     StagingLease S;
     YGZ_TRY(S.acquire(device));
     hipStream_t st = S->stream;
+    // not the lease's frame: a fixed header and a 2-D window copy, no pinned staging
     const size_t small = 256;  // pwb 100 | p 64 | px 8 | status 4
     uint8_t host_small[small];
     memcpy(host_small, patch_with_border, 100);
@@ -1909,18 +1910,18 @@ extern "C" int ygzfe_find_direct_projection_batch(const ygzfe_frame *const *ref,
     std::lock_guard<std::mutex> lk(ex->mu);
     hipStream_t st = ex->stream;
     const Plan &P = cur->plan->hp();
-    // in: [ref ptrs][scale][ref_index][kps][pt][T]  out: [px][level][ok]
-    const size_t o_sc = align16(sizeof(void *) * nref), o_ri = o_sc + align16(sizeof(float) * P.nlevels);
-    const size_t o_kp = o_ri + align16(4 * (size_t)n), o_pt = o_kp + align16(sizeof(ygzfe_kp) * n);
-    const size_t o_T = o_pt + align16(12 * (size_t)n), o_px = o_T + align16(sizeof(ygzfe_se3) * n);
-    const size_t in_bytes = o_px + align16(8 * (size_t)n), out_bytes = (size_t)n * 13;
+    BlockLayout in{16}, out{16};  // in: [ref ptrs][scale][ref_index][kps][pt][T]  out: [px][level][ok]
+    const size_t o_ref = in.take(nref, sizeof(void *)), o_sc = in.take(P.nlevels, sizeof(float)), o_ri = in.take(n, 4);
+    const size_t o_kp = in.take(n, sizeof(ygzfe_kp)), o_pt = in.take(n, 12), o_T = in.take(n, sizeof(ygzfe_se3));
+    const size_t o_px = in.take(n, 8), in_bytes = in.size();
+    const size_t o_out = out.take(n, 13), out_bytes = out.end();  // px, level and ok, packed
     YGZ_TRY(ex->direct_hin.ensure(in_bytes));
     YGZ_TRY(ex->direct_hout.ensure(out_bytes));
-    YGZ_TRY(ex->direct_dev.ensure(in_bytes + align16(out_bytes)));
+    YGZ_TRY(ex->direct_dev.ensure(in_bytes + out.size()));
     uint8_t *h = ex->direct_hin.as<uint8_t>(), *d = ex->direct_dev.as<uint8_t>();
-    const uint8_t **ptrs = reinterpret_cast<const uint8_t **>(h);
+    const uint8_t **ptrs = at<const uint8_t *>(h, o_ref);
     for (int r = 0; r < nref; r++) ptrs[r] = ref[r]->pyr.as<uint8_t>();
-    float *sc = reinterpret_cast<float *>(h + o_sc);
+    float *sc = at<float>(h, o_sc);
     for (int l = 0; l < P.nlevels; l++) sc[l] = P.lv[l].scale;
     memcpy(h + o_ri, ref_index, 4 * (size_t)n);
     memcpy(h + o_kp, kp_ref, sizeof(ygzfe_kp) * n);
@@ -1928,16 +1929,15 @@ extern "C" int ygzfe_find_direct_projection_batch(const ygzfe_frame *const *ref,
     memcpy(h + o_T, T_cr, sizeof(ygzfe_se3) * n);
     memcpy(h + o_px, px_io, 8 * (size_t)n);
     YGZ_HIP(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, st));
-    float *dpx = reinterpret_cast<float *>(d + in_bytes);
-    int32_t *dlv = reinterpret_cast<int32_t *>(d + in_bytes + 8 * (size_t)n);
-    uint8_t *dok = d + in_bytes + 12 * (size_t)n;
+    float *dpx = at<float>(d, in_bytes + o_out);
+    int32_t *dlv = at<int32_t>(d, in_bytes + o_out + 8 * (size_t)n);
+    uint8_t *dok = d + in_bytes + o_out + 12 * (size_t)n;
     YGZ_HIP(hipMemcpyAsync(dpx, d + o_px, 8 * (size_t)n, hipMemcpyDeviceToDevice, st));
     const AlignLevels lv = levels_of(P);
-    YGZ_HIP(launch_find_direct(reinterpret_cast<const uint8_t *const *>(d), lv, cur->pyr.as<uint8_t>(), lv, P.nlevels,
-                               reinterpret_cast<const float *>(d + o_sc), ex->scales.inv_sigma2[1 < P.nlevels ? 1 : 0],
-                               *cam, n, reinterpret_cast<const int32_t *>(d + o_ri),
-                               reinterpret_cast<const ygzfe_kp *>(d + o_kp), reinterpret_cast<const float *>(d + o_pt),
-                               reinterpret_cast<const ygzfe_se3 *>(d + o_T), dpx, dlv, dok, st));
+    YGZ_HIP(launch_find_direct(at<const uint8_t *const>(d, o_ref), lv, cur->pyr.as<uint8_t>(), lv, P.nlevels,
+                               at<const float>(d, o_sc), ex->scales.inv_sigma2[1 < P.nlevels ? 1 : 0], *cam, n,
+                               at<const int32_t>(d, o_ri), at<const ygzfe_kp>(d, o_kp), at<const float>(d, o_pt),
+                               at<const ygzfe_se3>(d, o_T), dpx, dlv, dok, st));
     YGZ_HIP(hipMemcpyAsync(ex->direct_hout.p, dpx, out_bytes, hipMemcpyDeviceToHost, st));
     YGZ_HIP(hipStreamSynchronize(st));
     const uint8_t *ho = ex->direct_hout.as<uint8_t>();
@@ -2000,10 +2000,10 @@ static int search_direct_impl(const ygzfe_frame *const *ref, int n_ref, const yg
     std::vector<int32_t> slot_tcr((size_t)std::max(1, n_ref), -1);
     std::vector<ygzfe_se3> tab;
     tab.reserve(std::max(1, n_ref));
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t o_ptr = 0, o_sc = al(o_ptr + sizeof(void *) * std::max(1, n_ref));
-    const size_t o_ip = al(o_sc + 4 * kMaxLevels), o_pp = al(o_ip + 4 * ((size_t)n_points + 1));
-    const size_t o_it = al(o_pp + 8 * (size_t)n_points), o_tab = al(o_it + sizeof(DirectItem) * (size_t)n_items);
+    BlockLayout in{256}, out{256};
+    const size_t o_ptr = in.take(std::max(1, n_ref), sizeof(void *)), o_sc = in.take(kMaxLevels, 4);
+    const size_t o_ip = in.take((size_t)n_points + 1, 4), o_pp = in.take(n_points, 8);
+    const size_t o_it = in.take(n_items, sizeof(DirectItem));
     std::vector<int32_t> tcr_of((size_t)n_items);
     for (int k = 0; k < n_items; k++) {
         int &e = slot_tcr[ref_index[k]];
@@ -2016,20 +2016,20 @@ static int search_direct_impl(const ygzfe_frame *const *ref, int n_ref, const yg
             tcr_of[k] = e;
         }
     }
-    const size_t in_bytes = al(o_tab + sizeof(ygzfe_se3) * std::max<size_t>(1, tab.size()));
-    const size_t o_hdr = 0, o_pxo = 16, o_m = o_pxo + 8 * (size_t)n_points, o_st = o_m + 4 * (size_t)n_points;
-    const size_t back_bytes = o_st + 4 * (size_t)n_points;
-    const size_t o_pxi = al(back_bytes), o_ok = al(o_pxi + 8 * (size_t)n_items), out_bytes = al(o_ok + (size_t)n_items);
+    const size_t o_tab = in.take(std::max<size_t>(1, tab.size()), sizeof(ygzfe_se3)), in_bytes = in.size();
+    const size_t o_pxo = 16, o_m = o_pxo + 8 * (size_t)n_points, o_st = o_m + 4 * (size_t)n_points;
+    const size_t o_hdr = out.take(o_st + 4 * (size_t)n_points), back_bytes = out.end();  // goes back, packed
+    const size_t o_pxi = out.take(n_items, 8), o_ok = out.take(n_items), out_bytes = out.size();
     YGZ_TRY(ex->direct_hin.ensure(in_bytes));
     YGZ_TRY(ex->direct_hout.ensure(back_bytes));
     uint8_t *h = ex->direct_hin.as<uint8_t>();
-    const uint8_t **ptrs = (const uint8_t **)(h + o_ptr);
+    const uint8_t **ptrs = at<const uint8_t *>(h, o_ptr);
     for (int r = 0; r < n_ref; r++) ptrs[r] = ref[r]->pyr.as<uint8_t>();
-    float *sc = (float *)(h + o_sc);
+    float *sc = at<float>(h, o_sc);
     for (int l = 0; l < P.nlevels; l++) sc[l] = P.lv[l].scale;
     memcpy(h + o_ip, item_ptr, 4 * ((size_t)n_points + 1));
     memcpy(h + o_pp, px_proj, 8 * (size_t)n_points);
-    DirectItem *it = (DirectItem *)(h + o_it);
+    DirectItem *it = at<DirectItem>(h, o_it);
     for (int i = 0; i < n_points; i++)
         for (int k = item_ptr[i]; k < item_ptr[i + 1]; k++) {
             it[k].kp = kp_ref[k];
@@ -2042,12 +2042,12 @@ static int search_direct_impl(const ygzfe_frame *const *ref, int n_ref, const yg
     YGZ_TRY(ex->direct_dev.ensure(in_bytes + out_bytes));
     uint8_t *d = ex->direct_dev.as<uint8_t>(), *dout = d + in_bytes;
     YGZ_HIP(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, st));
-    YGZ_HIP(launch_search_direct((const uint8_t *const *)(d + o_ptr), levels_of(P), cur->pyr.as<uint8_t>(),
-                                 P.nlevels, (const float *)(d + o_sc), ex->scales.inv_sigma2[1 < P.nlevels ? 1 : 0],
-                                 *cam, n_cache, n_local, n_items, (const int32_t *)(d + o_ip), d + o_it,
-                                 (const ygzfe_se3 *)(d + o_tab), (const float *)(d + o_pp), (float *)(dout + o_pxi), dout + o_ok, border, grid_size,
-                                 cache_hit_th, (float *)(dout + o_pxo), (int32_t *)(dout + o_m),
-                                 (int32_t *)(dout + o_st), (int32_t *)(dout + o_hdr), st));
+    YGZ_HIP(launch_search_direct(at<const uint8_t *const>(d, o_ptr), levels_of(P), cur->pyr.as<uint8_t>(), P.nlevels,
+                                 at<const float>(d, o_sc), ex->scales.inv_sigma2[1 < P.nlevels ? 1 : 0], *cam, n_cache,
+                                 n_local, n_items, at<const int32_t>(d, o_ip), d + o_it, at<const ygzfe_se3>(d, o_tab),
+                                 at<const float>(d, o_pp), at<float>(dout, o_pxi), dout + o_ok, border, grid_size,
+                                 cache_hit_th, at<float>(dout, o_pxo), at<int32_t>(dout, o_m), at<int32_t>(dout, o_st),
+                                 at<int32_t>(dout, o_hdr), st));
     uint8_t *hb = ex->direct_hout.as<uint8_t>();
     YGZ_HIP(hipMemcpyAsync(hb, dout, back_bytes, hipMemcpyDeviceToHost, st));
     YGZ_HIP(hipStreamSynchronize(st));
@@ -2172,34 +2172,33 @@ extern "C" int ygzfe_search_local_map_direct(const ygzfe_frame *cur, const ygzfe
     YGZ_TRY(ensure_device(ex->device));
     std::lock_guard<std::mutex> lk(ex->mu);
     hipStream_t st = ex->stream;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    BlockLayout li{256}, lo{256};
     const size_t nk = (size_t)std::max(1, n_kf), N = (size_t)n;
     // in: [ref ptrs][kp ptrs][scale][kf_id][T_rw][T_cr][excluded] [world][normal][min][max][obs_ptr][skip] [obs_kf][obs_kp]
-    const size_t i_ref = 0, i_kpp = al(i_ref + 8 * nk), i_sc = al(i_kpp + 8 * nk), i_id = al(i_sc + 4 * kMaxLevels);
-    const size_t i_trw = al(i_id + 8 * nk), i_tcr = al(i_trw + 48 * nk), i_ex = al(i_tcr + sizeof(ygzfe_se3) * nk);
-    const size_t i_w = al(i_ex + nk), i_nr = al(i_w + 12 * N), i_mn = al(i_nr + 12 * N), i_mx = al(i_mn + 4 * N);
-    const size_t i_op = al(i_mx + 4 * N), i_sk = al(i_op + 4 * (N + 1)), i_ok = al(i_sk + N);
-    const size_t i_oq = al(i_ok + 4 * (size_t)n_obs), in_bytes = al(i_oq + 4 * (size_t)n_obs);
-    // back: [hdr][status][px_out][matched_kf][matched_kp][proj][view_cos][dist]
+    const size_t i_ref = li.take(nk, 8), i_kpp = li.take(nk, 8), i_sc = li.take(kMaxLevels, 4), i_id = li.take(nk, 8);
+    const size_t i_trw = li.take(nk, 48), i_tcr = li.take(nk, sizeof(ygzfe_se3)), i_ex = li.take(nk);
+    const size_t i_w = li.take(N, 12), i_nr = li.take(N, 12), i_mn = li.take(N, 4), i_mx = li.take(N, 4);
+    const size_t i_op = li.take(N + 1, 4), i_sk = li.take(N), i_ok = li.take(n_obs, 4), i_oq = li.take(n_obs, 4);
+    // back, packed: [hdr][status][px_out][matched_kf][matched_kp][proj][view_cos][dist]
     const size_t b_st = 16, b_px = b_st + 4 * N, b_mk = b_px + 8 * N, b_mp = b_mk + 4 * N, b_pj = b_mp + 4 * N;
-    const size_t b_vc = b_pj + 12 * N, b_ds = b_vc + 4 * N, back_bytes = b_ds + 4 * N;
+    const size_t b_vc = b_pj + 12 * N, b_ds = b_vc + 4 * N, b_hdr = lo.take(b_ds + 4 * N), back_bytes = lo.end();
     // scratch: [culled][cnt][bsum][sel_kf][sel_kp][item_ptr][n_items][px_proj][matched_item][items][px_item][ok_item]
     const size_t nblk = (N + kDirectSetupThreads - 1) / kDirectSetupThreads, M = (size_t)max_items;
-    const size_t s_cu = al(back_bytes), s_cn = al(s_cu + N), s_bs = al(s_cn + 4 * N), s_sf = al(s_bs + 4 * nblk);
-    const size_t s_sp = al(s_sf + 4 * kDirectMaxSel * N), s_ip = al(s_sp + 4 * kDirectMaxSel * N);
-    const size_t s_ni = al(s_ip + 4 * (N + 1)), s_pp = al(s_ni + 4), s_mi = al(s_pp + 8 * N), s_it = al(s_mi + 4 * N);
-    const size_t s_pi = al(s_it + sizeof(DirectItem) * M), s_oi = al(s_pi + 8 * M), out_bytes = al(s_oi + M);
+    const size_t nsel = kDirectMaxSel * N, s_cu = lo.take(N), s_cn = lo.take(N, 4), s_bs = lo.take(nblk, 4);
+    const size_t s_sf = lo.take(nsel, 4), s_sp = lo.take(nsel, 4), s_ip = lo.take(N + 1, 4), s_ni = lo.take(4);
+    const size_t s_pp = lo.take(N, 8), s_mi = lo.take(N, 4), s_it = lo.take(M, sizeof(DirectItem));
+    const size_t s_pi = lo.take(M, 8), s_oi = lo.take(M), in_bytes = li.size(), out_bytes = lo.size();
     YGZ_TRY(ex->direct_hin.ensure(in_bytes));
     YGZ_TRY(ex->direct_hout.ensure(back_bytes));
     YGZ_TRY(ex->direct_dev.ensure(in_bytes + out_bytes));
     uint8_t *h = ex->direct_hin.as<uint8_t>(), *d = ex->direct_dev.as<uint8_t>(), *dout = d + in_bytes;
-    const uint8_t **ptrs = (const uint8_t **)(h + i_ref);
-    const ygzfe_kp **kpp = (const ygzfe_kp **)(h + i_kpp);
+    const uint8_t **ptrs = at<const uint8_t *>(h, i_ref);
+    const ygzfe_kp **kpp = at<const ygzfe_kp *>(h, i_kpp);
     for (int k = 0; k < n_kf; k++) {
         ptrs[k] = kfs->ref[k]->pyr.as<uint8_t>();
         kpp[k] = kfs->ref[k]->kps.as<ygzfe_kp>();
     }
-    float *sc = (float *)(h + i_sc);
+    float *sc = at<float>(h, i_sc);
     for (int l = 0; l < P.nlevels; l++) sc[l] = P.lv[l].scale;
     if (n_kf > 0) {
         memcpy(h + i_id, kfs->kf_id, 8 * (size_t)n_kf);
@@ -2219,44 +2218,43 @@ extern "C" int ygzfe_search_local_map_direct(const ygzfe_frame *cur, const ygzfe
     }
     YGZ_HIP(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, st));
     DirectMapDev in;
-    in.world = (const float *)(d + i_w);
-    in.normal = (const float *)(d + i_nr);
-    in.min_dist = (const float *)(d + i_mn);
-    in.max_dist = (const float *)(d + i_mx);
+    in.world = at<const float>(d, i_w);
+    in.normal = at<const float>(d, i_nr);
+    in.min_dist = at<const float>(d, i_mn);
+    in.max_dist = at<const float>(d, i_mx);
     in.skip = d + i_sk;
-    in.obs_ptr = (const int32_t *)(d + i_op);
-    in.obs_kf = (const int32_t *)(d + i_ok);
-    in.obs_kp = (const int32_t *)(d + i_oq);
-    in.kf_id = (const int64_t *)(d + i_id);
+    in.obs_ptr = at<const int32_t>(d, i_op);
+    in.obs_kf = at<const int32_t>(d, i_ok);
+    in.obs_kp = at<const int32_t>(d, i_oq);
+    in.kf_id = at<const int64_t>(d, i_id);
     in.kf_excluded = d + i_ex;
-    in.T_rw = (const float *)(d + i_trw);
-    in.kf_kps = (const ygzfe_kp *const *)(d + i_kpp);
+    in.T_rw = at<const float>(d, i_trw);
+    in.kf_kps = at<const ygzfe_kp *const>(d, i_kpp);
     DirectMapWork w;
     w.culled = dout + s_cu;
-    w.cnt = (int32_t *)(dout + s_cn);
-    w.bsum = (int32_t *)(dout + s_bs);
-    w.sel_kf = (int32_t *)(dout + s_sf);
-    w.sel_kp = (int32_t *)(dout + s_sp);
-    w.item_ptr = (int32_t *)(dout + s_ip);
-    w.n_items = (int32_t *)(dout + s_ni);
+    w.cnt = at<int32_t>(dout, s_cn);
+    w.bsum = at<int32_t>(dout, s_bs);
+    w.sel_kf = at<int32_t>(dout, s_sf);
+    w.sel_kp = at<int32_t>(dout, s_sp);
+    w.item_ptr = at<int32_t>(dout, s_ip);
+    w.n_items = at<int32_t>(dout, s_ni);
     w.items = dout + s_it;
-    w.px_proj = (float *)(dout + s_pp);
-    w.px_item = (float *)(dout + s_pi);
+    w.px_proj = at<float>(dout, s_pp);
+    w.px_item = at<float>(dout, s_pi);
     w.ok_item = dout + s_oi;
-    w.matched_item = (int32_t *)(dout + s_mi);
-    w.hdr = (int32_t *)dout;
-    w.status = (int32_t *)(dout + b_st);
-    w.px_out = (float *)(dout + b_px);
-    w.matched_kf = (int32_t *)(dout + b_mk);
-    w.matched_kp = (int32_t *)(dout + b_mp);
-    w.proj = (float *)(dout + b_pj);
-    w.view_cos = (float *)(dout + b_vc);
-    w.dist = (float *)(dout + b_ds);
-    YGZ_HIP(launch_search_local_map((const uint8_t *const *)(d + i_ref), levels_of(P), cur->pyr.as<uint8_t>(),
-                                    P.nlevels, (const float *)(d + i_sc),
-                                    ex->scales.inv_sigma2[1 < P.nlevels ? 1 : 0], *cam, *view, cand->n_cache,
-                                    cand->n_local, n_sel, max_items, in, (const ygzfe_se3 *)(d + i_tcr), w, border,
-                                    grid_size, cache_hit_th, st));
+    w.matched_item = at<int32_t>(dout, s_mi);
+    w.hdr = at<int32_t>(dout, b_hdr);
+    w.status = at<int32_t>(dout, b_st);
+    w.px_out = at<float>(dout, b_px);
+    w.matched_kf = at<int32_t>(dout, b_mk);
+    w.matched_kp = at<int32_t>(dout, b_mp);
+    w.proj = at<float>(dout, b_pj);
+    w.view_cos = at<float>(dout, b_vc);
+    w.dist = at<float>(dout, b_ds);
+    YGZ_HIP(launch_search_local_map(at<const uint8_t *const>(d, i_ref), levels_of(P), cur->pyr.as<uint8_t>(), P.nlevels,
+                                    at<const float>(d, i_sc), ex->scales.inv_sigma2[1 < P.nlevels ? 1 : 0], *cam, *view,
+                                    cand->n_cache, cand->n_local, n_sel, max_items, in, at<const ygzfe_se3>(d, i_tcr),
+                                    w, border, grid_size, cache_hit_th, st));
     uint8_t *hb = ex->direct_hout.as<uint8_t>();
     YGZ_HIP(hipMemcpyAsync(hb, dout, back_bytes, hipMemcpyDeviceToHost, st));
     YGZ_HIP(hipStreamSynchronize(st));
@@ -2268,7 +2266,7 @@ extern "C" int ygzfe_search_local_map_direct(const ygzfe_frame *cur, const ygzfe
     if (out->view_cos) memcpy(out->view_cos, hb + b_vc, 4 * N);
     if (out->dist) memcpy(out->dist, hb + b_ds, 4 * N);
     int32_t hdr[2];
-    memcpy(hdr, hb, 8);
+    memcpy(hdr, hb + b_hdr, 8);
     if (cache_success) *cache_success = hdr[0];
     if (local_ran) *local_ran = hdr[1];
     return YGZFE_OK;
@@ -2329,29 +2327,26 @@ extern "C" int ygzfe_stereo_matches(const ygzfe_frame *left, const ygzfe_frame *
     YGZ_TRY(ensure_device(ex->device));
     std::lock_guard<std::mutex> lk(ex->mu);
     hipStream_t st = ex->stream;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    // in: [job][counts][kl][kr][dl][dr]  out: [u_right][depth][sad]
-    const size_t o_job = 0, o_cnt = al(sizeof(StereoJob)), o_kl = al(o_cnt + 8);
-    const size_t o_kr = al(o_kl + sizeof(ygzfe_kp) * (size_t)nl), o_dl = al(o_kr + sizeof(ygzfe_kp) * (size_t)nr);
-    const size_t o_dr = al(o_dl + 32 * (size_t)nl), in_bytes = al(o_dr + 32 * (size_t)nr);
-    const size_t o_u = in_bytes, o_d = al(o_u + 4 * (size_t)nl), o_s = al(o_d + 4 * (size_t)nl);
-    const size_t total = al(o_s + 4 * (size_t)nl);
-    YGZ_TRY(ex->direct_dev.ensure(total));
+    BlockLayout blk{256};  // one block, in: [job][counts][kl][kr][dl][dr]  out: [u_right][depth][sad]
+    const size_t o_job = blk.take(sizeof(StereoJob)), o_cnt = blk.take(8), o_kl = blk.take(nl, sizeof(ygzfe_kp));
+    const size_t o_kr = blk.take(nr, sizeof(ygzfe_kp)), o_dl = blk.take(nl, 32), o_dr = blk.take(nr, 32);
+    const size_t in_bytes = blk.size(), o_u = blk.take(nl, 4), o_d = blk.take(nl, 4), o_s = blk.take(nl, 4);
+    YGZ_TRY(ex->direct_dev.ensure(blk.size()));
     uint8_t *d = ex->direct_dev.as<uint8_t>();
     YGZ_TRY(ex->direct_hin.ensure(in_bytes));
     uint8_t *h = ex->direct_hin.as<uint8_t>();
     StereoJob J;
     J.left_pyr = left->pyr.as<uint8_t>();
     J.right_pyr = right->pyr.as<uint8_t>();
-    J.left_kps = (const ygzfe_kp *)(d + o_kl);
-    J.right_kps = (const ygzfe_kp *)(d + o_kr);
+    J.left_kps = at<const ygzfe_kp>(d, o_kl);
+    J.right_kps = at<const ygzfe_kp>(d, o_kr);
     J.left_desc = d + o_dl;
     J.right_desc = d + o_dr;
-    J.n_left = (const int *)(d + o_cnt);
-    J.n_right = (const int *)(d + o_cnt + 4);
-    J.u_right = (float *)(d + o_u);
-    J.depth = (float *)(d + o_d);
-    J.sad = (int *)(d + o_s);
+    J.n_left = at<const int>(d, o_cnt);
+    J.n_right = at<const int>(d, o_cnt + 4);
+    J.u_right = at<float>(d, o_u);
+    J.depth = at<float>(d, o_d);
+    J.sad = at<int>(d, o_s);
     memcpy(h + o_job, &J, sizeof(J));
     const int cnt[2] = {nl, nr};
     memcpy(h + o_cnt, cnt, 8);
@@ -2360,7 +2355,7 @@ extern "C" int ygzfe_stereo_matches(const ygzfe_frame *left, const ygzfe_frame *
     memcpy(h + o_dl, dl, 32 * (size_t)nl);
     if (nr) memcpy(h + o_dr, dr, 32 * (size_t)nr);
     YGZ_HIP(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, st));
-    YGZ_HIP(launch_stereo((const StereoJob *)(d + o_job), 1, nl, stereo_levels_of(P), mb, mbf, st));
+    YGZ_HIP(launch_stereo(at<const StereoJob>(d, o_job), 1, nl, stereo_levels_of(P), mb, mbf, st));
     YGZ_HIP(hipMemcpyAsync(u_right, d + o_u, 4 * (size_t)nl, hipMemcpyDeviceToHost, st));
     YGZ_HIP(hipMemcpyAsync(depth, d + o_d, 4 * (size_t)nl, hipMemcpyDeviceToHost, st));
     YGZ_HIP(hipStreamSynchronize(st));
@@ -2399,24 +2394,20 @@ extern "C" int ygzfe_stereo_from_rgbd(int device, const float *im_depth, int wid
         return YGZFE_EINVAL;
     }
     if (n == 0) return YGZFE_OK;
-    YGZ_TRY(ensure_device(device));
     StagingLease S;
     YGZ_TRY(S.acquire(device));
-    // in: [depth image][kps]  out: [u_right][depth]
-    const size_t img = 4 * (size_t)stride * height, o_k = align16(img);
-    const size_t in_bytes = o_k + align16(sizeof(ygzfe_kp) * (size_t)n), out_bytes = 8 * (size_t)n;
-    YGZ_TRY(S->hin.ensure(in_bytes));
-    YGZ_TRY(S->hout.ensure(out_bytes));
-    YGZ_TRY(S->dev.ensure(in_bytes + out_bytes));
+    BlockLayout in{16};  // in: [depth image][kps]  out: [u_right][depth]
+    const size_t o_img = in.take((size_t)stride * height, 4), o_k = in.take(n, sizeof(ygzfe_kp));
+    const size_t in_bytes = in.size(), out_bytes = 8 * (size_t)n;
+    YGZ_TRY(S.reserve(in_bytes, out_bytes));
     uint8_t *h = S->hin.as<uint8_t>(), *d = S->dev.as<uint8_t>();
-    memcpy(h, im_depth, 4 * ((size_t)(height - 1) * stride + width));  // the last row may end at `width`
+    memcpy(h + o_img, im_depth, 4 * ((size_t)(height - 1) * stride + width));  // the last row may end at `width`
     memcpy(h + o_k, kps, sizeof(ygzfe_kp) * (size_t)n);
-    YGZ_HIP(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, S->stream));
-    float *du = reinterpret_cast<float *>(d + in_bytes), *dd = du + n;
-    YGZ_HIP(launch_stereo_rgbd(reinterpret_cast<const float *>(d), 0, width, height, stride,
-                               reinterpret_cast<const ygzfe_kp *>(d + o_k), n, nullptr, n, 1, mbf, du, dd, S->stream));
-    YGZ_HIP(hipMemcpyAsync(S->hout.p, du, out_bytes, hipMemcpyDeviceToHost, S->stream));
-    YGZ_HIP(hipStreamSynchronize(S->stream));
+    YGZ_TRY(S.upload(in_bytes));
+    float *du = at<float>(d, in_bytes), *dd = du + n;
+    YGZ_HIP(launch_stereo_rgbd(at<const float>(d, o_img), 0, width, height, stride, at<const ygzfe_kp>(d, o_k), n,
+                               nullptr, n, 1, mbf, du, dd, S->stream));
+    YGZ_TRY(S.download(in_bytes, out_bytes));
     memcpy(u_right, S->hout.p, 4 * (size_t)n);
     memcpy(depth, S->hout.as<float>() + n, 4 * (size_t)n);
     return YGZFE_OK;
@@ -2645,15 +2636,15 @@ static int bow_one(ygzfe_vocab *v, const uint8_t *desc, int n, int levelsup, boo
     std::lock_guard<std::mutex> lk(v->mu);
     hipStream_t st = v->stream;
     const size_t N = (size_t)std::max(n, 1);
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     // device block: descriptors | word, weight, node (transform) | BowVector words, values,
     // FeatureVector nodes, features, the two counts (vectors); each part 256-B aligned
-    const size_t o_d = 0, o_w = al(32 * N), o_v = al(o_w + 4 * N), o_n = al(o_v + 8 * N);
-    const size_t o_bw = al(o_n + 4 * N), o_bv = al(o_bw + 4 * N), o_fn = al(o_bv + 8 * N), o_ff = al(o_fn + 4 * N);
-    const size_t o_c = al(o_ff + 4 * N), total = al(o_c + 16);
+    BlockLayout blk{256};
+    const size_t o_d = blk.take(N, 32), o_w = blk.take(N, 4), o_v = blk.take(N, 8), o_n = blk.take(N, 4);
+    const size_t o_bw = blk.take(N, 4), o_bv = blk.take(N, 8), o_fn = blk.take(N, 4), o_ff = blk.take(N, 4);
+    const size_t o_c = blk.take(16), total = blk.size();
     YGZ_TRY(v->scratch.ensure(total));
     uint8_t *d = v->scratch.as<uint8_t>();
-    int *cnt = (int *)(d + o_c);
+    int *cnt = at<int>(d, o_c);
     const size_t r0 = vectors ? o_bw : o_w, r1 = vectors ? o_c + 16 : o_n + 4 * N;  // the result block
     YGZ_TRY(v->hin.ensure(32 * N));
     YGZ_TRY(v->hout.ensure(r1 - r0));
@@ -2662,12 +2653,12 @@ static int bow_one(ygzfe_vocab *v, const uint8_t *desc, int n, int levelsup, boo
         YGZ_HIP(hipMemcpyAsync(d + o_d, v->hin.p, 32 * (size_t)n, hipMemcpyHostToDevice, st));
     }
     const int nn = v->n_words > 0 ? n : 0;  // transform() returns early on an empty vocabulary
-    YGZ_HIP(launch_bow_transform(v->dev(), d + o_d, 0, nullptr, nn, 1, levelsup, (int32_t *)(d + o_w),
-                                 (double *)(d + o_v), (int32_t *)(d + o_n), 0, st));
+    YGZ_HIP(launch_bow_transform(v->dev(), d + o_d, 0, nullptr, nn, 1, levelsup, at<int32_t>(d, o_w),
+                                 at<double>(d, o_v), at<int32_t>(d, o_n), 0, st));
     if (vectors)
-        YGZ_HIP(launch_bow_vectors(nullptr, nn, 1, (int32_t *)(d + o_w), (double *)(d + o_v), (int32_t *)(d + o_n), 0,
-                                   v->weighting, v->scoring, (int32_t *)(d + o_bw), (double *)(d + o_bv), cnt,
-                                   (int32_t *)(d + o_fn), (int32_t *)(d + o_ff), cnt + 1, 0, st));
+        YGZ_HIP(launch_bow_vectors(nullptr, nn, 1, at<int32_t>(d, o_w), at<double>(d, o_v), at<int32_t>(d, o_n), 0,
+                                   v->weighting, v->scoring, at<int32_t>(d, o_bw), at<double>(d, o_bv), cnt,
+                                   at<int32_t>(d, o_fn), at<int32_t>(d, o_ff), cnt + 1, 0, st));
     if (vectors || nn > 0) YGZ_HIP(hipMemcpyAsync(v->hout.p, d + r0, r1 - r0, hipMemcpyDeviceToHost, st));
     YGZ_HIP(hipStreamSynchronize(st));
     const uint8_t *h = v->hout.as<uint8_t>() - r0;  // h + o_x: part o_x of the block
@@ -2679,7 +2670,7 @@ static int bow_one(ygzfe_vocab *v, const uint8_t *desc, int n, int levelsup, boo
         }
         return YGZFE_OK;
     }
-    const int *hc = (const int *)(h + o_c);
+    const int *hc = at<int>(h, o_c);
     *n_words = hc[0];
     *n_fv = hc[1];
     if (hc[0] > 0) {
@@ -2858,23 +2849,23 @@ static int undistort_host(const ygzfe_undistort *u, const void *src, int src_str
         set_error("invalid argument");
         return YGZFE_EINVAL;
     }
-    YGZ_TRY(ensure_device(u->device));
     StagingLease S;
     YGZ_TRY(S.acquire(u->device));
-    const size_t row = (size_t)u->W * esize, img = row * u->H, o_d = align16(img);
-    YGZ_TRY(S->hin.ensure(img));
+    BlockLayout blk{16};  // device block: [source][remapped]
+    const size_t row = (size_t)u->W * esize, img = row * u->H, o_s = blk.take(img), o_d = blk.take(img);
+    YGZ_TRY(S->hin.ensure(img));  // not the lease's frame: the source goes up without its padding
     YGZ_TRY(S->hout.ensure(img));
-    YGZ_TRY(S->dev.ensure(o_d + img));
+    YGZ_TRY(S->dev.ensure(blk.end()));
     uint8_t *h = S->hin.as<uint8_t>(), *d = S->dev.as<uint8_t>();
     for (int y = 0; y < u->H; y++)
         memcpy(h + (size_t)y * row, static_cast<const uint8_t *>(src) + (size_t)y * src_stride * esize, row);
-    YGZ_HIP(hipMemcpyAsync(d, h, img, hipMemcpyHostToDevice, S->stream));
+    YGZ_HIP(hipMemcpyAsync(d + o_s, h, img, hipMemcpyHostToDevice, S->stream));
     if (esize == 4)
-        YGZ_HIP(launch_remap_f32(reinterpret_cast<const float *>(d), 0, u->W, u->H, u->W, u->map1.as<int16_t>(),
-                                 u->map2.as<uint16_t>(), reinterpret_cast<float *>(d + o_d), 0, u->W, 1, S->stream));
+        YGZ_HIP(launch_remap_f32(at<const float>(d, o_s), 0, u->W, u->H, u->W, u->map1.as<int16_t>(),
+                                 u->map2.as<uint16_t>(), at<float>(d, o_d), 0, u->W, 1, S->stream));
     else
-        YGZ_HIP(launch_remap_linear(d, 0, u->W, u->H, u->W, u->map1.as<int16_t>(), u->map2.as<uint16_t>(), u->boxes.p,
-                                    u->max_box, u->any_large, d + o_d, 0, u->W, 1, S->stream));
+        YGZ_HIP(launch_remap_linear(d + o_s, 0, u->W, u->H, u->W, u->map1.as<int16_t>(), u->map2.as<uint16_t>(),
+                                    u->boxes.p, u->max_box, u->any_large, d + o_d, 0, u->W, 1, S->stream));
     YGZ_HIP(hipMemcpyAsync(S->hout.p, d + o_d, img, hipMemcpyDeviceToHost, S->stream));
     YGZ_HIP(hipStreamSynchronize(S->stream));
     for (int y = 0; y < u->H; y++)
@@ -2986,15 +2977,6 @@ namespace {
 constexpr int kMatchTopK = 32;  // match.hip kTopList (J.topk stride)
 constexpr int kMatchCells = 64 * 48;  // FRAME_GRID_COLS x ROWS
 
-struct Arena {
-    size_t off = 0;
-    size_t take(size_t bytes) {
-        const size_t o = off;
-        off = (off + bytes + 255) & ~(size_t)255;
-        return o;
-    }
-};
-
 int match_frame_finish(ygzfe_match_frame *f, const ygzfe_bounds *bounds) {
     f->bounds = *bounds;
     // Frame.cc:296-297
@@ -3045,30 +3027,29 @@ int run_match(MatchCall &c) {
     // query descriptors of another match frame: uploaded on that frame's stream
     if (c.qframe && c.qframe != f && c.qframe->ev_ready) YGZ_HIP(hipStreamWaitEvent(st, c.qframe->ev_ready, 0));
     // device input layout
-    Arena ai;
-    const size_t o_q = ai.take(sizeof(ygzfe_match_query) * (size_t)std::max(nq, 1));
-    const size_t o_qd = c.qdesc_host ? ai.take((size_t)32 * std::max(c.n_qdesc, 1)) : 0;
-    const size_t o_qid = c.qid.empty() ? 0 : ai.take(sizeof(int32_t) * c.qid.size());
-    const size_t o_cp = c.cand_ptr.empty() ? 0 : ai.take(sizeof(int32_t) * c.cand_ptr.size());
-    const size_t o_c = c.cand_host ? ai.take(sizeof(int32_t) * (size_t)std::max(c.n_cand, 1)) : 0;
-    const size_t o_bl = c.blocked_host ? ai.take((size_t)std::max(n, 1)) : 0;
+    BlockLayout ai{256}, ao{256};
+    const size_t o_q = ai.take(std::max(nq, 1), sizeof(ygzfe_match_query));
+    const size_t o_qd = c.qdesc_host ? ai.take(std::max(c.n_qdesc, 1), 32) : 0;
+    const size_t o_qid = c.qid.empty() ? 0 : ai.take(c.qid.size(), sizeof(int32_t));
+    const size_t o_cp = c.cand_ptr.empty() ? 0 : ai.take(c.cand_ptr.size(), sizeof(int32_t));
+    const size_t o_c = c.cand_host ? ai.take(std::max(c.n_cand, 1), sizeof(int32_t)) : 0;
+    const size_t o_bl = c.blocked_host ? ai.take(std::max(n, 1)) : 0;
     // device outputs / scratch
-    Arena ao;
-    const size_t o_tout = ao.take(sizeof(int32_t) * (size_t)std::max(n, 1));
-    const size_t o_qout = ao.take(sizeof(int32_t) * (size_t)std::max(nq, 1));
-    const size_t o_nm = ao.take(4 * sizeof(int32_t));
-    const size_t out_bytes = ao.off;
-    const size_t o_topk = ao.take(sizeof(uint64_t) * kMatchTopK * (size_t)std::max(nq, 1));
-    const size_t o_ncand = ao.take(sizeof(int32_t) * (size_t)std::max(nq, 1));
-    const size_t o_push = ao.take(sizeof(int32_t) * (size_t)std::max(nq, 1));
-    const size_t o_qang = ao.take(sizeof(float) * (size_t)std::max(nq, 1));
-    YGZ_TRY(f->out.ensure(ao.off));
+    const size_t o_tout = ao.take(std::max(n, 1), sizeof(int32_t));
+    const size_t o_qout = ao.take(std::max(nq, 1), sizeof(int32_t));
+    const size_t o_nm = ao.take(4, sizeof(int32_t));
+    const size_t out_bytes = ao.size();  // what comes back; the scratch parts follow
+    const size_t o_topk = ao.take((size_t)kMatchTopK * std::max(nq, 1), sizeof(uint64_t));
+    const size_t o_ncand = ao.take(std::max(nq, 1), sizeof(int32_t));
+    const size_t o_push = ao.take(std::max(nq, 1), sizeof(int32_t));
+    const size_t o_qang = ao.take(std::max(nq, 1), sizeof(float));
+    YGZ_TRY(f->out.ensure(ao.size()));
     uint8_t *dout = f->out.as<uint8_t>();
     // The inputs stay in page-locked host memory that the kernels read directly (one
     // pass in k_match_topk, which copies what the decisions need into HBM): no H2D
     // copy and no copy-to-kernel dependency on the stream.  The previous call
     // synchronised its stream, so the staging is free.
-    YGZ_TRY(f->hin.ensure(ai.off));
+    YGZ_TRY(f->hin.ensure(ai.size()));
     uint8_t *h = f->hin.as<uint8_t>(), *din = nullptr;
     YGZ_HIP(hipHostGetDevicePointer(reinterpret_cast<void **>(&din), h, 0));
     MatchJob J;
@@ -3084,20 +3065,20 @@ int run_match(MatchCall &c) {
     J.min_y = f->bounds.min_y;
     J.inv_w = f->inv_w;
     J.inv_h = f->inv_h;
-    J.q = reinterpret_cast<const ygzfe_match_query *>(din + o_q);
+    J.q = at<const ygzfe_match_query>(din, o_q);
     J.qdesc = c.qdesc_host ? din + o_qd : c.qdesc_dev;
-    J.qid = c.qid.empty() ? nullptr : reinterpret_cast<const int32_t *>(din + o_qid);
+    J.qid = c.qid.empty() ? nullptr : at<const int32_t>(din, o_qid);
     J.nq = nq;
-    J.cand_ptr = c.cand_ptr.empty() ? nullptr : reinterpret_cast<const int32_t *>(din + o_cp);
-    J.cand = c.cand_host ? reinterpret_cast<const int32_t *>(din + o_c) : nullptr;
+    J.cand_ptr = c.cand_ptr.empty() ? nullptr : at<const int32_t>(din, o_cp);
+    J.cand = c.cand_host ? at<const int32_t>(din, o_c) : nullptr;
     J.blocked0 = c.blocked_host ? din + o_bl : nullptr;
-    J.topk = reinterpret_cast<uint64_t *>(dout + o_topk);
-    J.ncand = reinterpret_cast<int32_t *>(dout + o_ncand);
-    J.qangle = reinterpret_cast<float *>(dout + o_qang);
-    J.train_out = reinterpret_cast<int32_t *>(dout + o_tout);
-    J.query_out = reinterpret_cast<int32_t *>(dout + o_qout);
-    J.pushes = reinterpret_cast<int32_t *>(dout + o_push);
-    J.nmatches = reinterpret_cast<int32_t *>(dout + o_nm);
+    J.topk = at<uint64_t>(dout, o_topk);
+    J.ncand = at<int32_t>(dout, o_ncand);
+    J.qangle = at<float>(dout, o_qang);
+    J.train_out = at<int32_t>(dout, o_tout);
+    J.query_out = at<int32_t>(dout, o_qout);
+    J.pushes = at<int32_t>(dout, o_push);
+    J.nmatches = at<int32_t>(dout, o_nm);
     if (nq) memcpy(h + o_q, c.q.data(), sizeof(ygzfe_match_query) * nq);
     if (c.qdesc_host && c.n_qdesc) memcpy(h + o_qd, c.qdesc_host, (size_t)32 * c.n_qdesc);
     if (!c.qid.empty()) memcpy(h + o_qid, c.qid.data(), sizeof(int32_t) * c.qid.size());
@@ -3112,8 +3093,8 @@ int run_match(MatchCall &c) {
     if (direct) {  // k_match_resolve writes each output once, straight into page-locked host memory
         uint8_t *hod = nullptr;
         YGZ_HIP(hipHostGetDevicePointer(reinterpret_cast<void **>(&hod), f->hout.p, 0));
-        J.train_out = reinterpret_cast<int32_t *>(hod + o_tout);
-        J.nmatches = reinterpret_cast<int32_t *>(hod + o_nm);
+        J.train_out = at<int32_t>(hod, o_tout);
+        J.nmatches = at<int32_t>(hod, o_nm);
     }
     YGZ_HIP(launch_match(J, c.mode, c.th_dist, c.check_ori, c.nnratio, max_passes, st));
     if (!direct) YGZ_HIP(hipMemcpyAsync(f->hout.p, dout, out_bytes, hipMemcpyDeviceToHost, st));
@@ -3406,22 +3387,19 @@ int ygzfe_pose_optimization(int device, const ygzfe_camera *cam, float bf, const
             set_error("row %d: octave %d outside [0, %d)", i, kps[i].octave, n_levels);
             return YGZFE_EINVAL;
         }
-    YGZ_TRY(ensure_device(device));
     StagingLease S;
     YGZ_TRY(S.acquire(device));
     // in: [problem_ptr 2][cam][bf][T_init][inv_sigma2][kps][xw][u_right][present]  out: [result][outlier]
     const size_t rows = (size_t)(n > 0 ? n : 1);
-    const size_t o_cam = 16, o_bf = o_cam + 16, o_T = o_bf + 16, o_sig = o_T + 32;
-    const size_t o_kps = o_sig + align16((size_t)n_levels * 4), o_xw = o_kps + align16(rows * sizeof(ygzfe_kp));
-    const size_t o_ur = o_xw + align16(rows * 12), o_pr = o_ur + align16(rows * 4);
-    const size_t in_bytes = o_pr + align16(rows);
-    const size_t o_flags = align16(sizeof(ygzfe_pose_opt_result)), out_bytes = o_flags + align16(rows);
-    YGZ_TRY(S->hin.ensure(in_bytes));
-    YGZ_TRY(S->hout.ensure(out_bytes));
-    YGZ_TRY(S->dev.ensure(in_bytes + out_bytes));
-    uint8_t *h = S->hin.as<uint8_t>(), *d = S->dev.as<uint8_t>();
     const int32_t ptr[2] = {0, n};
-    memcpy(h, ptr, sizeof(ptr));
+    BlockLayout in{16}, out{16};
+    const size_t o_ptr = in.take(sizeof(ptr)), o_cam = in.take(sizeof(*cam)), o_bf = in.take(sizeof(bf));
+    const size_t o_T = in.take(sizeof(*T_cw_init)), o_sig = in.take(n_levels, 4), o_kps = in.take(rows, sizeof(*kps));
+    const size_t o_xw = in.take(rows, 12), o_ur = in.take(rows, 4), o_pr = in.take(rows), in_bytes = in.size();
+    const size_t o_res = out.take(sizeof(ygzfe_pose_opt_result)), o_flags = out.take(rows), out_bytes = out.size();
+    YGZ_TRY(S.reserve(in_bytes, out_bytes));
+    uint8_t *h = S->hin.as<uint8_t>(), *d = S->dev.as<uint8_t>();
+    memcpy(h + o_ptr, ptr, sizeof(ptr));
     memcpy(h + o_cam, cam, sizeof(*cam));
     memcpy(h + o_bf, &bf, sizeof(bf));
     memcpy(h + o_T, T_cw_init, sizeof(*T_cw_init));
@@ -3432,17 +3410,15 @@ int ygzfe_pose_optimization(int device, const ygzfe_camera *cam, float bf, const
         if (u_right) memcpy(h + o_ur, u_right, (size_t)n * 4);
         memcpy(h + o_pr, present, (size_t)n);
     }
-    YGZ_HIP(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, S->stream));
+    YGZ_TRY(S.upload(in_bytes));
     uint8_t *dout = d + in_bytes;
     YGZ_TRY(ygzfe_pose_optimization_batch(
-        device, 1, reinterpret_cast<const int32_t *>(d), reinterpret_cast<const ygzfe_camera *>(d + o_cam),
-        reinterpret_cast<const float *>(d + o_bf), reinterpret_cast<const ygzfe_se3 *>(d + o_T),
-        reinterpret_cast<const ygzfe_kp *>(d + o_kps), u_right ? reinterpret_cast<const float *>(d + o_ur) : nullptr,
-        reinterpret_cast<const float *>(d + o_xw), d + o_pr, reinterpret_cast<const float *>(d + o_sig), n_levels,
-        dout + o_flags, reinterpret_cast<ygzfe_pose_opt_result *>(dout), S->stream));
-    YGZ_HIP(hipMemcpyAsync(S->hout.p, dout, out_bytes, hipMemcpyDeviceToHost, S->stream));
-    YGZ_HIP(hipStreamSynchronize(S->stream));
-    memcpy(result, S->hout.p, sizeof(*result));
+        device, 1, at<const int32_t>(d, o_ptr), at<const ygzfe_camera>(d, o_cam), at<const float>(d, o_bf),
+        at<const ygzfe_se3>(d, o_T), at<const ygzfe_kp>(d, o_kps), u_right ? at<const float>(d, o_ur) : nullptr,
+        at<const float>(d, o_xw), d + o_pr, at<const float>(d, o_sig), n_levels, dout + o_flags,
+        at<ygzfe_pose_opt_result>(dout, o_res), S->stream));
+    YGZ_TRY(S.download(in_bytes, out_bytes));
+    memcpy(result, S->hout.as<uint8_t>() + o_res, sizeof(*result));
     if (result->rounds > 0) {  // mvbOutlier is written where a map point is present only
         const uint8_t *flags = S->hout.as<uint8_t>() + o_flags;
         for (int i = 0; i < n; i++)
