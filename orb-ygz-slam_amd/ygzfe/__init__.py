@@ -16,6 +16,8 @@ import os
 
 import numpy as np
 
+from . import _abi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 PKG_ROOT = os.path.dirname(_HERE)
 LIB_PATH = os.environ.get("YGZFE_LIB") or os.path.join(PKG_ROOT, "lib", "libygzfe.so")  # YGZFE_LIB: A/B builds
@@ -71,12 +73,16 @@ ALIGN_RESULT_DTYPE = np.dtype([("q", "<f4", 4), ("t", "<f4", 3), ("n_visible", "
 _lib = None
 
 
+def _load(path, prefix, entries, hint=""):
+    if not os.path.exists(path):
+        raise YgzfeError(f"{path} missing: run `make -C orb-ygz-slam_amd`{hint}")
+    return _abi.declare(path, prefix, entries)
+
+
 def lib():
     """Load libygzfe.so; raise loudly when it is absent (no fallback)."""
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise YgzfeError(f"{LIB_PATH} missing: run `make -C orb-ygz-slam_amd` (or __graft_entry__.build())")
         # torch ships its own libamdhip64.so.7; whichever copy loads first
         # serves the whole process, and torch refuses to run on a runtime it
         # was not built with.  Load torch's first so device pointers and
@@ -85,10 +91,7 @@ def lib():
             import torch  # noqa: F401
         except ImportError:
             pass
-        L = C.CDLL(LIB_PATH)
-        L.ygzfe_last_error.restype = C.c_char_p
-        L.ygzfe_batch_stream.restype = C.c_void_p
-        _lib = L
+        _lib = _load(LIB_PATH, "ygzfe_", _abi.YGZFE, " (or __graft_entry__.build())")
     return _lib
 
 
@@ -109,9 +112,7 @@ def device_count():
 
 def slot_bytes(kp_cap):
     """Bytes of one offline-sequence result slot (ygzfe_slot_bytes)."""
-    L = lib()
-    L.ygzfe_slot_bytes.restype = C.c_size_t
-    return int(L.ygzfe_slot_bytes(kp_cap))
+    return int(lib().ygzfe_slot_bytes(kp_cap))
 
 
 def orb_plan(nfeatures, scale_factor, nlevels, ini_th=20, min_th=7, width=752, height=480, blur=BLUR_CV4):
@@ -124,23 +125,35 @@ def orb_plan(nfeatures, scale_factor, nlevels, ini_th=20, min_th=7, width=752, h
             "umax": um.tolist()}
 
 
-class Frame:
+def _created(what, *args):
+    """The handle that ygzfe_<what>(*args, &handle) makes."""
+    h = C.c_void_p()
+    _check(getattr(lib(), "ygzfe_" + what)(*args, C.byref(h)), what)
+    return h
+
+
+class _Handle:
+    """Owner of the C handle .h (a c_void_p) that the function named _destroy frees.  Whoever destroys the handle
+    through lib() directly sets .h to None."""
+    _destroy = None
+
+    def __del__(self):
+        if getattr(self, "h", None) and self.h.value and _lib is not None:
+            getattr(_lib, self._destroy)(self.h)
+            self.h = None
+
+
+class Frame(_Handle):
     """Device-resident pyramid (Frame::mvImagePyramid)."""
+    _destroy = "ygzfe_frame_destroy"
 
     def __init__(self, extractor, width, height):
         self.ex = extractor
         self.width, self.height = width, height
-        self.h = C.c_void_p()
-        _check(lib().ygzfe_frame_create(extractor.h, width, height, C.byref(self.h)), "frame_create")
-
-    def __del__(self):
-        if getattr(self, "h", None) and self.h.value and _lib is not None:
-            _lib.ygzfe_frame_destroy(self.h)
-            self.h = None
+        self.h = _created("frame_create", extractor.h, width, height)
 
     def level(self, l):
-        w = C.c_int()
-        h = C.c_int()
+        w, h = C.c_int(), C.c_int()
         _check(lib().ygzfe_frame_level(self.h, l, C.byref(w), C.byref(h), None, 0), "frame_level")
         out = np.zeros((h.value, w.value), np.uint8)
         _check(lib().ygzfe_frame_level(self.h, l, None, None, _p(out), w.value), "frame_level")
@@ -163,20 +176,15 @@ class Frame:
         return int(lib().ygzfe_frame_keypoint_count(self.h))
 
 
-class ORBextractor:
+class ORBextractor(_Handle):
     """ORBextractor(nfeatures, scaleFactor, nlevels, iniThFAST, minThFAST) (ORBextractor.h:53-57)."""
+    _destroy = "ygzfe_extractor_destroy"
 
     def __init__(self, nfeatures=500, scaleFactor=1.2, nlevels=8, iniThFAST=20, minThFAST=7, device=0,
                  blur=BLUR_CV4):
         self.params = OrbParams(nfeatures, scaleFactor, nlevels, iniThFAST, minThFAST, blur)
         self.nlevels = nlevels
-        self.h = C.c_void_p()
-        _check(lib().ygzfe_extractor_create(C.byref(self.params), device, C.byref(self.h)), "extractor_create")
-
-    def __del__(self):
-        if getattr(self, "h", None) and self.h.value and _lib is not None:
-            _lib.ygzfe_extractor_destroy(self.h)
-            self.h = None
+        self.h = _created("extractor_create", C.byref(self.params), device)
 
     # getters (ORBextractor.h:87-109)
     def GetLevels(self):
@@ -293,23 +301,17 @@ def fast10_detect(img, barrier, rois, sse=True, cap=None, device=0):
     return [xy[r, :counts[r]].copy() for r in range(n)]
 
 
-class Undistort:
+class Undistort(_Handle):
     """Frame::ComputeImagePyramid's undistortion (Frame.cc:775-790): the CV_16SC2
     initUndistortRectifyMap maps, built on the device once per camera, and the
     INTER_LINEAR remap applied per frame."""
+    _destroy = "ygzfe_undistort_destroy"
 
     def __init__(self, cam, dist, width, height, device=0):
         cam = cam if isinstance(cam, Camera) else Camera(*[float(c) for c in cam])
         d = np.ascontiguousarray(dist, np.float32).ravel()
         self.width, self.height, self.device = width, height, device
-        self.h = C.c_void_p()
-        _check(lib().ygzfe_undistort_create(device, C.byref(cam), _p(d) if len(d) else None, len(d), width, height,
-                                            C.byref(self.h)), "undistort_create")
-
-    def __del__(self):
-        if getattr(self, "h", None) and self.h.value and _lib is not None:
-            _lib.ygzfe_undistort_destroy(self.h)
-            self.h = None
+        self.h = _created("undistort_create", device, C.byref(cam), _p(d) if len(d) else None, len(d), width, height)
 
     def maps(self):
         """(map1 int16[H, W, 2], map2 uint16[H, W]) -- OpenCV's CV_16SC2 + CV_16UC1 pair."""
@@ -319,15 +321,13 @@ class Undistort:
         return m1, m2
 
     def apply_device(self, d_src, src_pitch, src_stride, d_dst, dst_pitch, dst_stride, n_images, stream=None):
-        _check(lib().ygzfe_undistort_apply_device(self.h, C.c_void_p(d_src), C.c_size_t(src_pitch), src_stride,
-                                                  C.c_void_p(d_dst), C.c_size_t(dst_pitch), dst_stride, n_images,
-                                                  C.c_void_p(stream)), "undistort_apply")
+        _check(lib().ygzfe_undistort_apply_device(self.h, d_src, src_pitch, src_stride, d_dst, dst_pitch, dst_stride,
+                                                  n_images, stream), "undistort_apply")
 
     def apply_f32_device(self, d_src, src_pitch, src_stride, d_dst, dst_pitch, dst_stride, n_images, stream=None):
         """remap of n CV_32F device images (pitch / stride in floats): Frame.cc:799-804."""
-        _check(lib().ygzfe_undistort_apply_f32_device(self.h, C.c_void_p(d_src), C.c_size_t(src_pitch), src_stride,
-                                                      C.c_void_p(d_dst), C.c_size_t(dst_pitch), dst_stride, n_images,
-                                                      C.c_void_p(stream)), "undistort_apply_f32")
+        _check(lib().ygzfe_undistort_apply_f32_device(self.h, d_src, src_pitch, src_stride, d_dst, dst_pitch,
+                                                      dst_stride, n_images, stream), "undistort_apply_f32")
 
     def remap_image(self, image):
         """cv::remap(mImGray / mImRight, ..., INTER_LINEAR) on a host u8 image (Frame.cc:786-797)."""
@@ -399,19 +399,14 @@ class Bounds(C.Structure):
     _fields_ = [("min_x", C.c_float), ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float)]
 
 
-class MatchFrame:
+class MatchFrame(_Handle):
     """The searched Frame's state on the device (mvKeys, mDescriptors, mvuRight, bounds;
     the 64 x 48 grid of AssignFeaturesToGrid is built there)."""
+    _destroy = "ygzfe_match_frame_destroy"
 
     def __init__(self, device=0):
-        self.h = C.c_void_p()
-        _check(lib().ygzfe_match_frame_create(device, C.byref(self.h)), "match_frame_create")
+        self.h = _created("match_frame_create", device)
         self.n = 0
-
-    def __del__(self):
-        if getattr(self, "h", None) and self.h.value and _lib is not None:
-            _lib.ygzfe_match_frame_destroy(self.h)
-            self.h = None
 
     def set(self, kps, desc, u_right=None, bounds=(0.0, 752.0, 0.0, 480.0)):
         kps = np.ascontiguousarray(kps, KP_DTYPE)
@@ -461,8 +456,8 @@ def search_projection_ratio(F, queries, q_desc, blocked=None, nnratio=0.6):
     bl = None if blocked is None else np.ascontiguousarray(blocked, np.uint8)
     out = np.zeros(max(F.n, 1), np.int32)
     nm = C.c_int()
-    _check(lib().ygzfe_search_projection_ratio(F.h, _p(q), _p(d), len(q), None if bl is None else _p(bl),
-                                               C.c_float(nnratio), _p(out), C.byref(nm)), "search_projection_ratio")
+    _check(lib().ygzfe_search_projection_ratio(F.h, _p(q), _p(d), len(q), None if bl is None else _p(bl), nnratio,
+                                               _p(out), C.byref(nm)), "search_projection_ratio")
     return out[:F.n], nm.value
 
 
@@ -471,8 +466,8 @@ def search_for_initialization(F1, F2, prev_matched, window_size=100, nnratio=0.9
     prev = np.ascontiguousarray(prev_matched, np.float32).reshape(-1, 2).copy()
     m12 = np.zeros(max(F1.n, 1), np.int32)
     nm = C.c_int()
-    _check(lib().ygzfe_search_for_initialization(F1.h, F2.h, _p(prev), window_size, C.c_float(nnratio),
-                                                 int(check_ori), _p(m12), C.byref(nm)), "search_for_initialization")
+    _check(lib().ygzfe_search_for_initialization(F1.h, F2.h, _p(prev), window_size, nnratio, int(check_ori),
+                                                 _p(m12), C.byref(nm)), "search_for_initialization")
     return m12[:F1.n], nm.value, prev
 
 
@@ -485,8 +480,7 @@ def search_by_bow(kf, F, kf_usable, fv_kf, fv_f, nnratio=0.7, check_ori=False):
     out = np.zeros(max(F.n, 1), np.int32)
     nm = C.c_int()
     _check(lib().ygzfe_search_by_bow(kf.h, F.h, _p(us), len(kn), _p(kn), _p(kp), _p(kfe), len(fn), _p(fn), _p(fp),
-                                     _p(ffe), C.c_float(nnratio), int(check_ori), _p(out), C.byref(nm)),
-           "search_by_bow")
+                                     _p(ffe), nnratio, int(check_ori), _p(out), C.byref(nm)), "search_by_bow")
     return out[:F.n], nm.value
 
 
@@ -544,7 +538,7 @@ def stereo_matches(left_frame, right_frame, kl, dl, kr, dr, mb, mbf):
     ur = np.zeros(len(kl), np.float32)
     dep = np.zeros(len(kl), np.float32)
     _check(lib().ygzfe_stereo_matches(left_frame.h, right_frame.h, _p(kl), _p(dl), len(kl), _p(kr), _p(dr), len(kr),
-                                      C.c_float(mb), C.c_float(mbf), _p(ur), _p(dep)), "stereo_matches")
+                                      mb, mbf, _p(ur), _p(dep)), "stereo_matches")
     return ur, dep
 
 
@@ -554,13 +548,14 @@ def stereo_from_rgbd(im_depth, kps, mbf, device=0):
     kps = np.ascontiguousarray(kps, KP_DTYPE)
     ur = np.zeros(len(kps), np.float32)
     dep = np.zeros(len(kps), np.float32)
-    _check(lib().ygzfe_stereo_from_rgbd(device, _p(im), im.shape[1], im.shape[0], im.shape[1], _p(kps), len(kps),
-                                        C.c_float(mbf), _p(ur), _p(dep)), "stereo_from_rgbd")
+    _check(lib().ygzfe_stereo_from_rgbd(device, _p(im), im.shape[1], im.shape[0], im.shape[1], _p(kps), len(kps), mbf,
+                                        _p(ur), _p(dep)), "stereo_from_rgbd")
     return ur, dep
 
 
-class Vocabulary:
+class Vocabulary(_Handle):
     """ORBVocabulary = TemplatedVocabulary<FORB::TDescriptor, FORB> (Thirdparty/DBoW2) in HBM."""
+    _destroy = "ygzfe_vocab_destroy"
 
     def __init__(self, handle, device):
         self.h, self.device = handle, device
@@ -574,29 +569,18 @@ class Vocabulary:
         is_leaf = np.ascontiguousarray(is_leaf, np.uint8)
         desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
         weight = np.ascontiguousarray(weight, np.float64)
-        h = C.c_void_p()
-        _check(lib().ygzfe_vocab_create(device, k, L, scoring, weighting, len(parent), _p(parent), _p(is_leaf),
-                                        _p(desc), _p(weight), C.byref(h)), "vocab_create")
-        return cls(h, device)
+        return cls(_created("vocab_create", device, k, L, scoring, weighting, len(parent), _p(parent), _p(is_leaf),
+                            _p(desc), _p(weight)), device)
 
     @classmethod
     def load_text(cls, path, device=0):
         """loadFromTextFile (TemplatedVocabulary.h:1362)."""
-        h = C.c_void_p()
-        _check(lib().ygzfe_vocab_load_text(device, str(path).encode(), C.byref(h)), "vocab_load_text")
-        return cls(h, device)
+        return cls(_created("vocab_load_text", device, str(path).encode()), device)
 
     @classmethod
     def load_binary(cls, path, device=0):
         """loadFromBinaryFile (TemplatedVocabulary.h:1478)."""
-        h = C.c_void_p()
-        _check(lib().ygzfe_vocab_load_binary(device, str(path).encode(), C.byref(h)), "vocab_load_binary")
-        return cls(h, device)
-
-    def __del__(self):
-        if getattr(self, "h", None) and self.h.value and _lib is not None:
-            _lib.ygzfe_vocab_destroy(self.h)
-            self.h = None
+        return cls(_created("vocab_load_binary", device, str(path).encode()), device)
 
     def transform_each(self, desc, levelsup=4):
         """transform(feature, word, weight, &nid, levelsup) per descriptor -> (word, weight, nid)."""
@@ -638,9 +622,8 @@ def search_direct_batch(ref_frames, cur_frame, cam, item_ptr, ref_index, kp_ref,
     px_out = np.zeros((max(n, 0), 2), np.float32)
     matched = np.zeros(max(n, 0), np.int32)
     _check(lib().ygzfe_search_direct_batch(refs, len(ref_frames), cur_frame.h, C.byref(cam), n, _p(item_ptr),
-                                           _p(ref_index), _p(kp_ref), _p(pt_ref), _p(T_cr), _p(px_proj),
-                                           C.c_float(border), _p(px_out), _p(matched)),
-           "search_direct_batch")
+                                           _p(ref_index), _p(kp_ref), _p(pt_ref), _p(T_cr), _p(px_proj), border,
+                                           _p(px_out), _p(matched)), "search_direct_batch")
     return px_out, matched
 
 
@@ -667,10 +650,9 @@ def search_local_points_direct(ref_frames, cur_frame, cam, n_cache, item_ptr, re
     cs, lr = C.c_int(), C.c_int()
     _check(lib().ygzfe_search_local_points_direct(refs, len(ref_frames), cur_frame.h, C.byref(cam), int(n_cache),
                                                   n - int(n_cache), _p(item_ptr), _p(ref_index), _p(kp_ref),
-                                                  _p(pt_ref), _p(T_cr), _p(px_proj), C.c_float(border), int(grid_size),
+                                                  _p(pt_ref), _p(T_cr), _p(px_proj), border, int(grid_size),
                                                   int(cache_hit_th), _p(px_out), _p(matched), _p(status),
-                                                  C.byref(cs), C.byref(lr)),
-           "search_local_points_direct")
+                                                  C.byref(cs), C.byref(lr)), "search_local_points_direct")
     return px_out, matched, status, cs.value, bool(lr.value)
 
 
@@ -754,14 +736,14 @@ def search_local_map_direct(kf_frames, cur_frame, cam, view, kf_id, kf_excluded,
                                                    "dist")])
     cs, lr = C.c_int(), C.c_int()
     _check(lib().ygzfe_search_local_map_direct(cur_frame.h, C.byref(cam), C.byref(view), C.byref(kfs), C.byref(cand),
-                                               int(n_sel), C.c_float(border), int(grid_size), int(cache_hit_th),
-                                               C.byref(out), C.byref(cs), C.byref(lr)),
-           "search_local_map_direct")
+                                               int(n_sel), border, int(grid_size), int(cache_hit_th), C.byref(out),
+                                               C.byref(cs), C.byref(lr)), "search_local_map_direct")
     return res, cs.value, bool(lr.value)
 
 
-class Batch:
+class Batch(_Handle):
     """Frames resident in HBM, one launch per stage (the bench / multi-GPU path)."""
+    _destroy = "ygzfe_batch_destroy"
 
     def __init__(self, params_or_extractor_args, device, width, height, max_frames):
         p = params_or_extractor_args
@@ -769,19 +751,10 @@ class Batch:
             p = OrbParams(*p)
         self.params = p
         self.device, self.width, self.height, self.max_frames = device, width, height, max_frames
-        self.h = C.c_void_p()
-        _check(lib().ygzfe_batch_create(C.byref(p), device, width, height, max_frames, C.byref(self.h)),
-               "batch_create")
-        pitch = C.c_size_t()
-        cap = C.c_int()
-        nl = C.c_int()
+        self.h = _created("batch_create", C.byref(p), device, width, height, max_frames)
+        pitch, cap, nl = C.c_size_t(), C.c_int(), C.c_int()
         _check(lib().ygzfe_batch_info(self.h, C.byref(pitch), C.byref(cap), C.byref(nl)), "batch_info")
         self.frame_pitch, self.kp_cap, self.nlevels = pitch.value, cap.value, nl.value
-
-    def __del__(self):
-        if getattr(self, "h", None) and self.h.value and _lib is not None:
-            _lib.ygzfe_batch_destroy(self.h)
-            self.h = None
 
     @property
     def stream(self):
@@ -802,19 +775,17 @@ class Batch:
         _check(lib().ygzfe_batch_upload_undistorted(self.h, und.h, _p(frames), len(frames)), "upload_undistorted")
 
     def undistort_device(self, und, d_raw, raw_pitch, n_frames, stream=None):
-        _check(lib().ygzfe_batch_undistort_device(self.h, und.h, C.c_void_p(d_raw), C.c_size_t(raw_pitch), n_frames,
-                                                  C.c_void_p(stream)), "batch_undistort")
+        _check(lib().ygzfe_batch_undistort_device(self.h, und.h, d_raw, raw_pitch, n_frames, stream), "batch_undistort")
 
     def bind(self, pyramids=0, kps=0, desc=0, counts=0):
-        _check(lib().ygzfe_batch_bind_buffers(self.h, C.c_void_p(pyramids or None), C.c_void_p(kps or None),
-                                              C.c_void_p(desc or None), C.c_void_p(counts or None)), "bind")
+        _check(lib().ygzfe_batch_bind_buffers(self.h, pyramids or None, kps or None, desc or None, counts or None),
+               "bind")
 
     def extract(self, n_frames, stream=None):
-        _check(lib().ygzfe_batch_extract(self.h, n_frames, C.c_void_p(stream)), "batch_extract")
+        _check(lib().ygzfe_batch_extract(self.h, n_frames, stream), "batch_extract")
 
     def extract_split(self, n_frames, kp_stream, desc_stream):
-        _check(lib().ygzfe_batch_extract_split(self.h, n_frames, C.c_void_p(kp_stream), C.c_void_p(desc_stream)),
-               "batch_extract_split")
+        _check(lib().ygzfe_batch_extract_split(self.h, n_frames, kp_stream, desc_stream), "batch_extract_split")
 
     def check(self):
         _check(lib().ygzfe_batch_check(self.h), "batch_check")
@@ -846,39 +817,31 @@ class Batch:
         return out
 
     def match(self, n_pairs, d_qframe, d_tframe, d_bi, d_bd, d_sd, stream=None):
-        _check(lib().ygzfe_batch_match(self.h, n_pairs, C.c_void_p(d_qframe), C.c_void_p(d_tframe), C.c_void_p(d_bi),
-                                       C.c_void_p(d_bd), C.c_void_p(d_sd), C.c_void_p(stream)), "batch_match")
+        _check(lib().ygzfe_batch_match(self.h, n_pairs, d_qframe, d_tframe, d_bi, d_bd, d_sd, stream), "batch_match")
 
     def sparse_align(self, n_pairs, d_ref_idx, d_cur_idx, d_xyz, d_usable, cam, max_level, min_level, d_T_init,
                      d_out, stream=None):
-        _check(lib().ygzfe_batch_sparse_align(self.h, n_pairs, C.c_void_p(d_ref_idx), C.c_void_p(d_cur_idx),
-                                              C.c_void_p(d_xyz), C.c_void_p(d_usable), C.byref(cam), max_level,
-                                              min_level, C.c_void_p(d_T_init), C.c_void_p(d_out),
-                                              C.c_void_p(stream)), "batch_sparse_align")
+        _check(lib().ygzfe_batch_sparse_align(self.h, n_pairs, d_ref_idx, d_cur_idx, d_xyz, d_usable, C.byref(cam),
+                                              max_level, min_level, d_T_init, d_out, stream), "batch_sparse_align")
 
     def stereo(self, n_pairs, d_left_idx, d_right_idx, mb, mbf, d_u_right, d_depth, stream=None):
-        _check(lib().ygzfe_batch_stereo(self.h, n_pairs, C.c_void_p(d_left_idx), C.c_void_p(d_right_idx),
-                                        C.c_float(mb), C.c_float(mbf), C.c_void_p(d_u_right), C.c_void_p(d_depth),
-                                        C.c_void_p(stream)), "batch_stereo")
+        _check(lib().ygzfe_batch_stereo(self.h, n_pairs, d_left_idx, d_right_idx, mb, mbf, d_u_right, d_depth, stream),
+               "batch_stereo")
 
     def stereo_rgbd(self, n_frames, d_depth_images, depth_pitch, stride, mbf, d_u_right, d_depth, stream=None):
-        _check(lib().ygzfe_batch_stereo_rgbd(self.h, n_frames, C.c_void_p(d_depth_images), C.c_size_t(depth_pitch),
-                                             stride, C.c_float(mbf), C.c_void_p(d_u_right), C.c_void_p(d_depth),
-                                             C.c_void_p(stream)), "batch_stereo_rgbd")
+        _check(lib().ygzfe_batch_stereo_rgbd(self.h, n_frames, d_depth_images, depth_pitch, stride, mbf, d_u_right,
+                                             d_depth, stream), "batch_stereo_rgbd")
 
     def compute_bow(self, vocab, n_frames, levelsup, d_bow_words, d_bow_values, d_n_words, d_fv_nodes, d_fv_feats,
                     d_n_fv, stream=None):
-        _check(lib().ygzfe_batch_compute_bow(self.h, vocab.h, n_frames, levelsup, C.c_void_p(d_bow_words),
-                                             C.c_void_p(d_bow_values), C.c_void_p(d_n_words),
-                                             C.c_void_p(d_fv_nodes), C.c_void_p(d_fv_feats), C.c_void_p(d_n_fv),
-                                             C.c_void_p(stream)), "batch_compute_bow")
+        _check(lib().ygzfe_batch_compute_bow(self.h, vocab.h, n_frames, levelsup, d_bow_words, d_bow_values, d_n_words,
+                                             d_fv_nodes, d_fv_feats, d_n_fv, stream), "batch_compute_bow")
 
     def pack_slots(self, frame_begin, n_frames, d_align, global_first, d_slots, slot_pitch, stream=None):
         """Device-side packing of the offline sequence mode's per-frame result slots
         (ygzfe_batch_pack_slots; layout in include/ygzfe.h and ygzfe.dist)."""
-        _check(lib().ygzfe_batch_pack_slots(self.h, frame_begin, n_frames, C.c_void_p(d_align or None), global_first,
-                                            C.c_void_p(d_slots), C.c_size_t(slot_pitch), C.c_void_p(stream)),
-               "batch_pack_slots")
+        _check(lib().ygzfe_batch_pack_slots(self.h, frame_begin, n_frames, d_align or None, global_first, d_slots,
+                                            slot_pitch, stream), "batch_pack_slots")
 
     def timing(self, enable=True):
         ms = (C.c_float * 16)()
@@ -894,16 +857,13 @@ _synth = None
 def synth():
     global _synth
     if _synth is None:
-        if not os.path.exists(SYNTH_PATH):
-            raise YgzfeError(f"{SYNTH_PATH} missing: run `make -C orb-ygz-slam_amd`")
-        _synth = C.CDLL(SYNTH_PATH)
-        _synth.ygzs_backproject_plane.restype = C.c_int
+        _synth = _load(SYNTH_PATH, "ygzs_", _abi.SYNTH)
     return _synth
 
 
 def synth_texture(seed, W, H):
     out = np.zeros((H, W), np.uint8)
-    synth().ygzs_texture(C.c_uint64(seed), W, H, _p(out))
+    synth().ygzs_texture(seed, W, H, _p(out))
     return out
 
 
@@ -922,10 +882,9 @@ def render_plane(tex, texel, plane_z, cam, q_cw, t_cw, W, H, noise_seed=0, noise
     tex = np.ascontiguousarray(tex, np.uint8)
     out = np.zeros((H, W), np.uint8)
     camv = np.array(cam, np.float32)
-    synth().ygzs_render_plane(_p(tex), tex.shape[1], tex.shape[0], C.c_double(texel), C.c_double(plane_z),
-                              _p(camv), _p(np.ascontiguousarray(q_cw, np.float32)),
-                              _p(np.ascontiguousarray(t_cw, np.float32)), W, H, C.c_uint64(noise_seed), noise_amp,
-                              _p(out))
+    synth().ygzs_render_plane(_p(tex), tex.shape[1], tex.shape[0], texel, plane_z, _p(camv),
+                              _p(np.ascontiguousarray(q_cw, np.float32)), _p(np.ascontiguousarray(t_cw, np.float32)),
+                              W, H, noise_seed, noise_amp, _p(out))
     return out
 
 
@@ -938,8 +897,7 @@ def backproject_plane(cam, q_cw, t_cw, uv, plane_z):
     ok = np.zeros(len(uv), np.uint8)
     P = np.zeros(3, np.float32)
     for i, (u, v) in enumerate(uv):
-        ok[i] = synth().ygzs_backproject_plane(_p(camv), _p(q), _p(t), C.c_float(u), C.c_float(v),
-                                               C.c_double(plane_z), _p(P))
+        ok[i] = synth().ygzs_backproject_plane(_p(camv), _p(q), _p(t), u, v, plane_z, _p(P))
         out[i] = P
     return out, ok
 
@@ -951,9 +909,7 @@ def _synth_hip_lib():
     global _synth_hip
     if _synth_hip is None:
         lib()  # torch's HIP runtime first (see lib())
-        if not os.path.exists(SYNTH_HIP_PATH):
-            raise YgzfeError(f"{SYNTH_HIP_PATH} missing: run `make -C orb-ygz-slam_amd`")
-        _synth_hip = C.CDLL(SYNTH_HIP_PATH)
+        _synth_hip = _load(SYNTH_HIP_PATH, "ygzs_", _abi.SYNTH_HIP)
     return _synth_hip
 
 
@@ -962,10 +918,8 @@ def render_plane_device(d_tex, tex_w, tex_h, texel, plane_z, cam, d_q, d_t, d_se
     """The synthetic plane sequence rendered on the device (synth/plane_points.hip):
     frame i (pose d_q[i], d_t[i], noise seed d_seeds[i]) -> d_out + i * pitch."""
     c = (C.c_float * 4)(*[float(v) for v in cam])
-    rc = _synth_hip_lib().ygzs_render_plane_device(C.c_void_p(d_tex), tex_w, tex_h, C.c_double(texel),
-                                                   C.c_double(plane_z), c, C.c_void_p(d_q), C.c_void_p(d_t),
-                                                   C.c_void_p(d_seeds), n_frames, W, H, noise_amp, C.c_void_p(d_out),
-                                                   C.c_size_t(pitch), C.c_void_p(stream))
+    rc = _synth_hip_lib().ygzs_render_plane_device(d_tex, tex_w, tex_h, texel, plane_z, c, d_q, d_t, d_seeds, n_frames,
+                                                   W, H, noise_amp, d_out, pitch, stream)
     if rc != 0:
         raise YgzfeError("render_plane_device launch failed")
 
@@ -974,8 +928,8 @@ def plane_points_device(d_kps, cap, n_frames, cam, d_r3, d_cz, plane_z, d_xyz, s
     """Synthetic map points for bench.py: back-project every keypoint of frame i
     onto the plane Z_w = plane_z (one fused HIP pass; synth/plane_points.hip)."""
     c = (C.c_float * 4)(*[float(v) for v in cam])
-    rc = _synth_hip_lib().ygzs_plane_points(C.c_void_p(d_kps), KP_DTYPE.itemsize // 4, cap, n_frames, c, C.c_void_p(d_r3),
-                                      C.c_void_p(d_cz), C.c_float(plane_z), C.c_void_p(d_xyz), C.c_void_p(stream))
+    rc = _synth_hip_lib().ygzs_plane_points(d_kps, KP_DTYPE.itemsize // 4, cap, n_frames, c, d_r3, d_cz, plane_z, d_xyz,
+                                            stream)
     if rc != 0:
         raise YgzfeError("plane_points launch failed")
 
@@ -993,7 +947,6 @@ POSE_OPT_RESULT_DTYPE = np.dtype({"names": ["Tq", "Tt", "q", "t", "n_corr", "n_i
                                   "formats": [("<f4", 4), ("<f4", 3), ("<f8", 4), ("<f8", 3), "<i4", "<i4", "<i4",
                                               ("<i4", 4), ("<i4", 4), ("<f8", 4)],
                                   "offsets": [0, 16, 32, 64, 88, 92, 96, 100, 116, 136], "itemsize": 168})
-assert C.sizeof(PoseOptResult) == POSE_OPT_RESULT_DTYPE.itemsize
 
 
 def pose_optimization(cam, bf, T_cw_init, kps, xw, present, inv_level_sigma2, u_right=None, outlier=None, device=0):
@@ -1011,7 +964,7 @@ def pose_optimization(cam, bf, T_cw_init, kps, xw, present, inv_level_sigma2, u_
     if len(pr) != n or len(out) != n or (ur is not None and len(ur) != n):
         raise YgzfeError("pose_optimization: array lengths differ")
     res = PoseOptResult()
-    _check(lib().ygzfe_pose_optimization(device, C.byref(cam), C.c_float(bf), C.byref(T_cw_init), n, _p(kps),
+    _check(lib().ygzfe_pose_optimization(device, C.byref(cam), bf, C.byref(T_cw_init), n, _p(kps),
                                          None if ur is None else _p(ur), _p(xw), _p(pr), _p(sig), len(sig), _p(out),
                                          C.byref(res)), "pose_optimization")
     return res, out
@@ -1044,10 +997,10 @@ def pose_optimization_batch(problem_ptr, cam, bf, T_init, kps, u_right, xw, pres
         results = torch.zeros((max(P, 0), POSE_OPT_RESULT_DTYPE.itemsize), dtype=torch.uint8, device=present.device)
     elif results.numel() != P * POSE_OPT_RESULT_DTYPE.itemsize or results.dtype != torch.uint8:
         raise YgzfeError("pose_optimization_batch: results must be uint8 [P, 168]")
-    vp = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    vp = torch.Tensor.data_ptr
     stream = torch.cuda.current_stream(present.device).cuda_stream
     _check(lib().ygzfe_pose_optimization_batch(device, P, vp(problem_ptr), vp(cam), vp(bf), vp(T_init), vp(kps),
                                                None if u_right is None else vp(u_right), vp(xw), vp(present),
                                                vp(inv_level_sigma2), int(inv_level_sigma2.numel()), vp(outlier),
-                                               vp(results), C.c_void_p(stream)), "pose_optimization_batch")
+                                               vp(results), stream), "pose_optimization_batch")
     return results
