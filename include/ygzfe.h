@@ -298,6 +298,61 @@ int ygzfe_search_by_bow(ygzfe_match_frame *kf, ygzfe_match_frame *F, const uint8
                         const int32_t *f_nodes, const int32_t *f_ptr, const int32_t *f_feats, float nnratio,
                         int check_ori, int32_t *f_match, int *nmatches);
 
+/* ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo)
+ * (ORBmatcher.cc:597-746, CheckDistEpipolarLine :136-153) for one keyframe against
+ * n_nb neighbours at once (LocalMapping::CreateNewMapPoints, LocalMapping.cc:1009-1042):
+ * one packed upload, two launches, one download and one synchronisation per call.
+ *
+ * Inputs.  has_mp1[kf1.n] / has_mp2: GetMapPoint(i) != NULL.  FeatureVectors are node-sorted
+ * CSR as in ygzfe_search_by_bow: KF1's is (n1_nodes, nodes1, ptr1[n1_nodes + 1], feats1), and
+ * every KF1 feature is listed at most once (DBoW2 gives a feature one node).  The neighbours'
+ * arrays are concatenated: neighbour k owns rows mp2_ptr[k] .. mp2_ptr[k+1] of has_mp2
+ * (exactly kf2[k].n of them) and nodes fv2_ptr[k] .. fv2_ptr[k+1] of nodes2; ptr2 has
+ * fv2_ptr[n_nb] + 1 entries and indexes feats2 globally (node j's features are
+ * feats2[ptr2[j] .. ptr2[j+1]), indices into kf2[k]); mp2_ptr[0] = fv2_ptr[0] = ptr2[0] = 0.
+ * F12 [n_nb][9] row-major; epipole [n_nb][2] = (ex, ey) as :603-609 form them (the caller's
+ * matrix types); level_sigma2 / scale_factors [n_levels] = pKF2->mvLevelSigma2 /
+ * mvScaleFactors.  A match frame without u_right has no stereo keypoint.
+ *
+ * Semantics.  The node walk is the lower-bound merge of :625-716.  KF1 feature idx1 of a
+ * shared node takes part when !has_mp1[idx1] (:638) and, if only_stereo, u_right1[idx1] >= 0
+ * (:641-645).  Its candidates are the KF2 features of the same node in list order; idx2 is
+ * accepted when !has_mp2[idx2] (:660), the stereo filter passes (:663-667), dist <= 50
+ * (TH_LOW, :673), if neither side is stereo
+ * !((ex-x2)*(ex-x2) + (ey-y2)*(ey-y2) < 100.0f * scale_factors[oct2]) in float (:678-683),
+ * and the epipolar test holds (:136-153): float32, each operation rounded once, nothing fused,
+ * a = (x1*F[0] + y1*F[3]) + F[6] (b, c with columns 1, 2), num = (a*x2 + b*y2) + c,
+ * den = a*a + b*b, rejected when den == 0, dsqr = (num*num)/den, and in double
+ * (double)dsqr < 3.84 * (double)level_sigma2[oct2].  Comparisons with NaN behave as written.
+ * This reference never writes vbMatched2 (:616 and :660 are its only uses), so features do not
+ * interact.  `dist > bestDist` skips and an equal distance replaces (:673, :685-688): the
+ * match is the smallest accepted distance, and among equal distances the last position in
+ * the node's list (not the largest index).  With check_ori (:696-705, :718-734) rot = angle1 -
+ * angle2 (+360 if negative), bin = round(rot * (1.0f/30)), 30 -> 0 (angles in [0, 360)),
+ * ComputeThreeMaxima keeps three bins and matches in the others become -1.
+ *
+ * matches12 [n_nb][kf1.n]: the KF2 index or -1 (vMatchedPairs = the rows >= 0 in ascending
+ * idx1); nmatches [n_nb]: the return values.  Results are the same on every run.
+ * YGZFE_EINVAL, before anything is launched or written: a neighbour keypoint's octave outside
+ * [0, n_levels), a feature index out of range, a KF1 feature listed twice, ranges that
+ * decrease, frames on different devices.  n_nb == 0, kf1.n == 0, an empty FeatureVector and a
+ * neighbour with no keypoints are valid and give no matches. */
+int ygzfe_search_for_triangulation_batch(ygzfe_match_frame *kf1, const uint8_t *has_mp1, int n1_nodes,
+                                         const int32_t *nodes1, const int32_t *ptr1, const int32_t *feats1, int n_nb,
+                                         ygzfe_match_frame *const *kf2, const int32_t *mp2_ptr, const uint8_t *has_mp2,
+                                         const int32_t *fv2_ptr, const int32_t *nodes2, const int32_t *ptr2,
+                                         const int32_t *feats2, const float *F12, const float *epipole,
+                                         const float *level_sigma2, const float *scale_factors, int n_levels,
+                                         int only_stereo, int check_ori, int32_t *matches12, int32_t *nmatches);
+/* The same for one neighbour (n_nb = 1): has_mp2[kf2.n], (n2_nodes, nodes2, ptr2, feats2) its
+ * FeatureVector, F12[9], epipole[2], matches12[kf1.n], nmatches[1]. */
+int ygzfe_search_for_triangulation(ygzfe_match_frame *kf1, const uint8_t *has_mp1, int n1_nodes, const int32_t *nodes1,
+                                   const int32_t *ptr1, const int32_t *feats1, ygzfe_match_frame *kf2,
+                                   const uint8_t *has_mp2, int n2_nodes, const int32_t *nodes2, const int32_t *ptr2,
+                                   const int32_t *feats2, const float *F12, const float *epipole,
+                                   const float *level_sigma2, const float *scale_factors, int n_levels,
+                                   int only_stereo, int check_ori, int32_t *matches12, int32_t *nmatches);
+
 /* ------------------------------------------------------------------------ */
 /* SparseImgAlign (SparseImageAlign.h:37-60)                                 */
 typedef struct ygzfe_align_result {

@@ -3353,6 +3353,163 @@ extern "C" int ygzfe_search_by_bow(ygzfe_match_frame *kf, ygzfe_match_frame *F, 
     return YGZFE_OK;
 }
 
+// ORBmatcher::SearchForTriangulation (ORBmatcher.cc:597-746) for all neighbours of one keyframe: the node
+// walks and the argument checks on the host, then one packed H2D, k_tri_search + k_tri_votes, one D2H.
+extern "C" int ygzfe_search_for_triangulation_batch(
+    ygzfe_match_frame *kf1, const uint8_t *has_mp1, int n1_nodes, const int32_t *nodes1, const int32_t *ptr1,
+    const int32_t *feats1, int n_nb, ygzfe_match_frame *const *kf2, const int32_t *mp2_ptr, const uint8_t *has_mp2,
+    const int32_t *fv2_ptr, const int32_t *nodes2, const int32_t *ptr2, const int32_t *feats2, const float *F12,
+    const float *epipole, const float *level_sigma2, const float *scale_factors, int n_levels, int only_stereo,
+    int check_ori, int32_t *matches12, int32_t *nmatches) {
+    if (!kf1 || n_nb < 0 || n1_nodes < 0 || n_levels <= 0 || !level_sigma2 || !scale_factors ||
+        (kf1->n > 0 && !has_mp1) || (n1_nodes > 0 && (!nodes1 || !ptr1)) ||
+        (n_nb > 0 && (!kf2 || !mp2_ptr || !fv2_ptr || !F12 || !epipole || !nmatches || (kf1->n > 0 && !matches12)))) {
+        set_error("invalid argument");
+        return YGZFE_EINVAL;
+    }
+    if (n_nb == 0) return YGZFE_OK;
+    const int n1 = kf1->n;
+    // KF1's FeatureVector: ranges in order, every feature in range and in one node only (DBoW2: one node per feature)
+    const int n_feats1 = n1_nodes > 0 ? ptr1[n1_nodes] : 0;
+    if (n1_nodes > 0 && (ptr1[0] != 0 || n_feats1 < 0 || (n_feats1 > 0 && !feats1))) {
+        set_error("KF1 FeatureVector: ptr1 must start at 0 and feats1 be given");
+        return YGZFE_EINVAL;
+    }
+    for (int k = 0; k < n1_nodes; k++)
+        if (ptr1[k] > ptr1[k + 1]) { set_error("KF1 FeatureVector: ptr1 decreases at node %d", k); return YGZFE_EINVAL; }
+    std::vector<uint8_t> seen1((size_t)n1, 0);
+    for (int a = 0; a < n_feats1; a++) {
+        const int idx = feats1[a];
+        if (idx < 0 || idx >= n1) { set_error("KF1 feature index %d out of range", idx); return YGZFE_EINVAL; }
+        if (seen1[idx]) { set_error("KF1 feature %d is listed in two nodes", idx); return YGZFE_EINVAL; }
+        seen1[idx] = 1;
+    }
+    if (mp2_ptr[0] != 0 || fv2_ptr[0] != 0) { set_error("mp2_ptr and fv2_ptr must start at 0"); return YGZFE_EINVAL; }
+    for (int k = 0; k < n_nb; k++) {
+        const ygzfe_match_frame *f = kf2[k];
+        if (!f) { set_error("neighbour %d is null", k); return YGZFE_EINVAL; }
+        if (f->device != kf1->device) { set_error("frames on different devices"); return YGZFE_EINVAL; }
+        if (mp2_ptr[k + 1] - mp2_ptr[k] != f->n) {
+            set_error("neighbour %d: has_mp2 holds %d rows for %d keypoints", k, mp2_ptr[k + 1] - mp2_ptr[k], f->n);
+            return YGZFE_EINVAL;
+        }
+        if (fv2_ptr[k + 1] < fv2_ptr[k]) { set_error("fv2_ptr decreases at neighbour %d", k); return YGZFE_EINVAL; }
+        for (int i = 0; i < f->n; i++)  // level_sigma2 / scale_factors are indexed by any candidate's octave
+            if (f->host_kps[i].octave < 0 || f->host_kps[i].octave >= n_levels) {
+                set_error("neighbour %d keypoint %d: octave %d outside [0, %d)", k, i, f->host_kps[i].octave, n_levels);
+                return YGZFE_EINVAL;
+            }
+    }
+    const int n2_nodes = fv2_ptr[n_nb], n_feats2 = n2_nodes > 0 && ptr2 ? ptr2[n2_nodes] : 0;
+    if ((mp2_ptr[n_nb] > 0 && !has_mp2) || (n2_nodes > 0 && (!nodes2 || !ptr2)) || n_feats2 < 0 ||
+        (n_feats2 > 0 && !feats2) || (n2_nodes > 0 && ptr2[0] != 0)) {
+        set_error("invalid argument");
+        return YGZFE_EINVAL;
+    }
+    for (int k = 0; k < n_nb; k++)
+        for (int j = fv2_ptr[k]; j < fv2_ptr[k + 1]; j++) {
+            if (ptr2[j] > ptr2[j + 1]) { set_error("neighbour %d FeatureVector: ptr2 decreases", k); return YGZFE_EINVAL; }
+            for (int a = ptr2[j]; a < ptr2[j + 1]; a++)
+                if (feats2[a] < 0 || feats2[a] >= kf2[k]->n) {
+                    set_error("neighbour %d feature index %d out of range", k, feats2[a]);
+                    return YGZFE_EINVAL;
+                }
+        }
+    // :625-716 per neighbour: the lower-bound merge of the two node lists; every KF1 feature of a shared
+    // node without a MapPoint (:638) is one row over that node's KF2 features
+    std::vector<TriRow> rows;
+    for (int k = 0; k < n_nb; k++) {
+        const int32_t *n2 = nodes2 + fv2_ptr[k], *p2 = ptr2 + fv2_ptr[k];
+        const int m2 = fv2_ptr[k + 1] - fv2_ptr[k];
+        int it1 = 0, it2 = 0;
+        while (it1 < n1_nodes && it2 < m2) {
+            if (nodes1[it1] == n2[it2]) {
+                if (p2[it2 + 1] > p2[it2])
+                    for (int a = ptr1[it1]; a < ptr1[it1 + 1]; a++)
+                        if (!has_mp1[feats1[a]]) rows.push_back(TriRow{k, feats1[a], p2[it2], p2[it2 + 1]});
+                it1++;
+                it2++;
+            } else if (nodes1[it1] < n2[it2]) {
+                it1 = (int)(std::lower_bound(nodes1 + it1, nodes1 + n1_nodes, n2[it2]) - nodes1);
+            } else {
+                it2 = (int)(std::lower_bound(n2 + it2, n2 + m2, nodes1[it1]) - n2);
+            }
+        }
+    }
+    const size_t n_out = (size_t)n_nb * n1;
+    if (rows.empty()) {  // nothing to search: no device work
+        std::fill(matches12, matches12 + n_out, -1);
+        std::fill(nmatches, nmatches + n_nb, 0);
+        return YGZFE_OK;
+    }
+    StagingLease S;
+    YGZ_TRY(S.acquire(kf1->device));
+    // in: [neighbour table][rows][feats2][sigma2][scale][has_mp2]   out: [matches12 n_nb x n1][nmatches n_nb]
+    BlockLayout in{16}, out{16};
+    const size_t o_nb = in.take(n_nb, sizeof(TriNeighbour)), o_rows = in.take(rows.size(), sizeof(TriRow));
+    const size_t o_f2 = in.take(n_feats2, 4), o_sig = in.take(n_levels, 4), o_sc = in.take(n_levels, 4);
+    const size_t o_mp = in.take(std::max(mp2_ptr[n_nb], 1)), in_bytes = in.size();
+    const size_t o_m = out.take(n_out, 4), o_nm = out.take(n_nb, 4), out_bytes = out.size();
+    YGZ_TRY(S.reserve(in_bytes, out_bytes));
+    uint8_t *h = S->hin.as<uint8_t>(), *d = S->dev.as<uint8_t>(), *dout = d + in_bytes;
+    TriNeighbour *tab = at<TriNeighbour>(h, o_nb);
+    // the frames' uploads (ygzfe_match_frame_set is asynchronous on each frame's own stream) come first
+    if (kf1->ev_ready) YGZ_HIP(hipStreamWaitEvent(S->stream, kf1->ev_ready, 0));
+    for (int k = 0; k < n_nb; k++) {
+        const ygzfe_match_frame *f = kf2[k];
+        if (f->ev_ready) YGZ_HIP(hipStreamWaitEvent(S->stream, f->ev_ready, 0));
+        TriNeighbour &N = tab[k];
+        N.kps = f->kps.as<ygzfe_kp>();
+        N.desc = f->desc.as<uint8_t>();
+        N.u_right = f->has_uright ? f->uright.as<float>() : nullptr;
+        N.mp_off = mp2_ptr[k];
+        memcpy(N.F, F12 + 9 * (size_t)k, sizeof(N.F));
+        N.ex = epipole[2 * k];
+        N.ey = epipole[2 * k + 1];
+    }
+    memcpy(h + o_rows, rows.data(), rows.size() * sizeof(TriRow));
+    memcpy(h + o_f2, feats2, (size_t)n_feats2 * 4);
+    memcpy(h + o_sig, level_sigma2, (size_t)n_levels * 4);
+    memcpy(h + o_sc, scale_factors, (size_t)n_levels * 4);
+    if (mp2_ptr[n_nb] > 0) memcpy(h + o_mp, has_mp2, (size_t)mp2_ptr[n_nb]);
+    YGZ_TRY(S.upload(in_bytes));
+    TriJob J;
+    J.kps1 = kf1->kps.as<ygzfe_kp>();
+    J.desc1 = kf1->desc.as<uint8_t>();
+    J.u_right1 = kf1->has_uright ? kf1->uright.as<float>() : nullptr;
+    J.n1 = n1;
+    J.n_nb = n_nb;
+    J.n_rows = (int)rows.size();
+    J.nb = at<const TriNeighbour>(d, o_nb);
+    J.rows = at<const TriRow>(d, o_rows);
+    J.feats2 = at<const int32_t>(d, o_f2);
+    J.has_mp2 = d + o_mp;
+    J.level_sigma2 = at<const float>(d, o_sig);
+    J.scale_factors = at<const float>(d, o_sc);
+    J.only_stereo = only_stereo != 0;
+    J.check_ori = check_ori != 0;
+    J.matches12 = at<int32_t>(dout, o_m);
+    J.nmatches = at<int32_t>(dout, o_nm);
+    YGZ_HIP(hipMemsetAsync(J.matches12, 0xFF, n_out * 4, S->stream));  // -1: vMatches12's initial value (:617)
+    YGZ_HIP(launch_triangulation(J, S->stream));
+    YGZ_TRY(S.download(in_bytes, out_bytes));
+    memcpy(matches12, S->hout.as<uint8_t>() + o_m, n_out * 4);
+    memcpy(nmatches, S->hout.as<uint8_t>() + o_nm, (size_t)n_nb * 4);
+    return YGZFE_OK;
+}
+
+extern "C" int ygzfe_search_for_triangulation(
+    ygzfe_match_frame *kf1, const uint8_t *has_mp1, int n1_nodes, const int32_t *nodes1, const int32_t *ptr1,
+    const int32_t *feats1, ygzfe_match_frame *kf2, const uint8_t *has_mp2, int n2_nodes, const int32_t *nodes2,
+    const int32_t *ptr2, const int32_t *feats2, const float *F12, const float *epipole, const float *level_sigma2,
+    const float *scale_factors, int n_levels, int only_stereo, int check_ori, int32_t *matches12, int32_t *nmatches) {
+    if (!kf2 || n2_nodes < 0) { set_error("invalid argument"); return YGZFE_EINVAL; }
+    const int32_t mp2_ptr[2] = {0, kf2->n}, fv2_ptr[2] = {0, n2_nodes};
+    return ygzfe_search_for_triangulation_batch(kf1, has_mp1, n1_nodes, nodes1, ptr1, feats1, 1, &kf2, mp2_ptr, has_mp2,
+                                                fv2_ptr, nodes2, ptr2, feats2, F12, epipole, level_sigma2,
+                                                scale_factors, n_levels, only_stereo, check_ori, matches12, nmatches);
+}
+
 // ------------------------------------------------------------------ pose-only optimisation
 // Optimizer::PoseOptimization (Optimizer.cc:1656-1842), poseopt.hip
 int ygzfe_pose_optimization_batch(int device, int n_problems, const int32_t *d_problem_ptr,

@@ -98,6 +98,31 @@ bool match_resolves(int n_train, int nq, int mode, int max_passes);  // launch_m
 hipError_t launch_match(const MatchJob &J, int mode, int th_dist, int check_ori, float nnratio, int max_passes,
                         hipStream_t st);
 
+// ORBmatcher::SearchForTriangulation (ORBmatcher.cc:597-746), one keyframe against n_nb neighbours
+struct TriNeighbour {  // one neighbour: its match frame's device arrays, its part of has_mp2, F12 and epipole
+    const ygzfe_kp *kps;
+    const uint8_t *desc;
+    const float *u_right;  // null: no keypoint is stereo
+    int32_t mp_off;
+    float F[9], ex, ey;
+};
+struct TriRow { int32_t nb, idx1, c0, c1; };  // KF1 feature idx1 against feats2[c0 .. c1) of neighbour nb
+struct TriJob {
+    const ygzfe_kp *kps1;
+    const uint8_t *desc1;
+    const float *u_right1;  // null: no keypoint is stereo
+    int n1, n_nb, n_rows;
+    const TriNeighbour *nb;
+    const TriRow *rows;
+    const int32_t *feats2;
+    const uint8_t *has_mp2;
+    const float *level_sigma2, *scale_factors;
+    int only_stereo, check_ori;
+    int32_t *matches12;  // [n_nb][n1], -1 everywhere on entry
+    int32_t *nmatches;   // [n_nb]
+};
+hipError_t launch_triangulation(const TriJob &J, hipStream_t st);
+
 // align.hip
 struct AlignLevels {
     int w[kMaxLevels], h[kMaxLevels];

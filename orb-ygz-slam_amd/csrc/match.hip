@@ -6,6 +6,7 @@
 //   SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, ws)    :375-478    mode INIT
 //   SearchByBoW(pKF, F, vpMapPointMatches)                             :155-263    mode BOW
 //   ComputeThreeMaxima                                                 :1471-1502
+//   SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo) :597-746   (the mapping side; at the end)
 //
 // The reference runs one query after another, and a query's candidates
 // depend on the assignments of the queries before it (a keypoint matched to
@@ -937,6 +938,121 @@ hipError_t launch_match(const MatchJob &J, int mode, int th_dist, int check_ori,
         hipLaunchKernelGGL(k_match_replay, dim3(1), dim3(64), replay_lds_bytes(n, mode), st, J, mode, th_dist,
                            check_ori, nnratio, stage_kv);
     }
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo) (ORBmatcher.cc:597-746) for one
+// keyframe against all its neighbours.  This reference never writes vbMatched2, so a KF1 feature's
+// result does not depend on the features before it: its best candidate is the smallest accepted
+// distance, and among equal distances the last position in the node's list (`dist > bestDist` skips,
+// an equal distance replaces).  One row = (neighbour, idx1, the node's range of feats2).
+//
+//  k_tri_search  kTriLanes lanes per row stride over the node's candidates; every predicate of the
+//                reference's inner loop on each, a min-reduction over (dist << 32 | ~position).
+//  k_tri_votes   one workgroup per neighbour: the rotation histogram (integer counts in LDS),
+//                ComputeThreeMaxima, the removals and nmatches.
+constexpr int kTriLanes = 16, kTriThreads = 256;
+constexpr int kTriThLow = 50;  // ORBmatcher::TH_LOW (ORBmatcher.cc:36)
+
+__global__ __launch_bounds__(kTriThreads) void k_tri_search(const TriJob J) {
+    const int g = (blockIdx.x * kTriThreads + threadIdx.x) / kTriLanes, sub = threadIdx.x % kTriLanes;
+    const bool live = g < J.n_rows;
+    const TriRow R = J.rows[live ? g : J.n_rows - 1];  // a group past the end repeats the last row, writes nothing
+    const TriNeighbour *N = J.nb + R.nb;
+    const float x1 = J.kps1[R.idx1].x, y1 = J.kps1[R.idx1].y;
+    const bool stereo1 = J.u_right1 && J.u_right1[R.idx1] >= 0;  // :641
+    uint64_t best = ~0ull;
+    if (!J.only_stereo || stereo1) {  // :643-645
+        const uint4 *p1 = reinterpret_cast<const uint4 *>(J.desc1 + (size_t)32 * R.idx1);
+        const uint4 d1a = p1[0], d1b = p1[1];
+        // CheckDistEpipolarLine (:136-153): l = x1' F12 = [a b c], each operation rounded once
+        const float a = (x1 * N->F[0] + y1 * N->F[3]) + N->F[6];
+        const float b = (x1 * N->F[1] + y1 * N->F[4]) + N->F[7];
+        const float c = (x1 * N->F[2] + y1 * N->F[5]) + N->F[8];
+        const float den = a * a + b * b;
+        const float ex = N->ex, ey = N->ey;
+        for (int i = R.c0 + sub; i < R.c1; i += kTriLanes) {
+            const int idx2 = J.feats2[i];
+            if (J.has_mp2[N->mp_off + idx2]) continue;                      // :660
+            const bool stereo2 = N->u_right && N->u_right[idx2] >= 0;       // :663
+            if (J.only_stereo && !stereo2) continue;                        // :665-667
+            const uint4 *p2 = reinterpret_cast<const uint4 *>(N->desc + (size_t)32 * idx2);
+            const uint4 d2a = p2[0], d2b = p2[1];
+            const int dist = __popc(d1a.x ^ d2a.x) + __popc(d1a.y ^ d2a.y) + __popc(d1a.z ^ d2a.z) +
+                             __popc(d1a.w ^ d2a.w) + __popc(d1b.x ^ d2b.x) + __popc(d1b.y ^ d2b.y) +
+                             __popc(d1b.z ^ d2b.z) + __popc(d1b.w ^ d2b.w);
+            if (dist > kTriThLow) continue;                                  // :673 (bestDist: the reduction)
+            const float x2 = N->kps[idx2].x, y2 = N->kps[idx2].y;
+            const int oct2 = N->kps[idx2].octave;
+            if (!stereo1 && !stereo2) {                                      // :678-683
+                const float distex = ex - x2, distey = ey - y2;
+                if (distex * distex + distey * distey < 100.0f * J.scale_factors[oct2]) continue;
+            }
+            const float num = (a * x2 + b * y2) + c;
+            if (den == 0) continue;                                          // :147
+            const float dsqr = num * num / den;
+            if (!((double)dsqr < 3.84 * (double)J.level_sigma2[oct2])) continue;  // :152, in double
+            const uint64_t key = ((uint64_t)dist << 32) | (0xFFFFFFFFu - (uint32_t)(i - R.c0));
+            best = key < best ? key : best;
+        }
+    }
+#pragma unroll
+    for (int o = kTriLanes / 2; o >= 1; o >>= 1) {
+        const uint32_t lo = __shfl_xor((uint32_t)best, o, kTriLanes), hi = __shfl_xor((uint32_t)(best >> 32), o, kTriLanes);
+        const uint64_t other = ((uint64_t)hi << 32) | lo;
+        best = other < best ? other : best;
+    }
+    if (live && sub == 0 && best != ~0ull)
+        J.matches12[(size_t)R.nb * J.n1 + R.idx1] = J.feats2[R.c0 + (int)(0xFFFFFFFFu - (uint32_t)best)];
+}
+
+__global__ __launch_bounds__(kTriThreads) void k_tri_votes(const TriJob J) {
+    __shared__ int s_hist[64];  // rot_bin's range; ComputeThreeMaxima reads the first kHisto
+    __shared__ int s_keep[3], s_sum[kTriThreads / 64];
+    const int tid = threadIdx.x;
+    const TriNeighbour *N = J.nb + blockIdx.x;
+    int32_t *m = J.matches12 + (size_t)blockIdx.x * J.n1;
+    if (tid < 64) s_hist[tid] = 0;
+    __syncthreads();
+    if (J.check_ori) {  // :696-705
+        for (int i = tid; i < J.n1; i += kTriThreads) {
+            const int v = m[i];
+            if (v >= 0) atomicAdd(&s_hist[rot_bin(J.kps1[i].angle, N->kps[v].angle)], 1);
+        }
+        __syncthreads();
+        if (tid == 0) three_maxima(s_hist, s_keep[0], s_keep[1], s_keep[2]);  // :719-723
+        __syncthreads();
+    }
+    int cnt = 0;
+    for (int i = tid; i < J.n1; i += kTriThreads) {
+        const int v = m[i];
+        if (v < 0) continue;
+        if (J.check_ori) {  // :725-732
+            const int bin = rot_bin(J.kps1[i].angle, N->kps[v].angle);
+            if (bin != s_keep[0] && bin != s_keep[1] && bin != s_keep[2]) {
+                m[i] = -1;
+                continue;
+            }
+        }
+        cnt++;
+    }
+    cnt = wave_sum_i(cnt);
+    if ((tid & 63) == 0) s_sum[tid >> 6] = cnt;
+    __syncthreads();
+    if (tid == 0) {
+        int tot = 0;
+        for (int k = 0; k < kTriThreads / 64; k++) tot += s_sum[k];
+        J.nmatches[blockIdx.x] = tot;
+    }
+}
+
+hipError_t launch_triangulation(const TriJob &J, hipStream_t st) {
+    if (J.n_rows > 0) {
+        const int groups = kTriThreads / kTriLanes;
+        hipLaunchKernelGGL(k_tri_search, dim3((J.n_rows + groups - 1) / groups), dim3(kTriThreads), 0, st, J);
+    }
+    if (J.n_nb > 0) hipLaunchKernelGGL(k_tri_votes, dim3(J.n_nb), dim3(kTriThreads), 0, st, J);
     return hipGetLastError();
 }
 

@@ -484,6 +484,66 @@ def search_by_bow(kf, F, kf_usable, fv_kf, fv_f, nnratio=0.7, check_ori=False):
     return out[:F.n], nm.value
 
 
+def _fv(fv):
+    """(nodes, ptr, feats) of a FeatureVector as int32 arrays; ptr of an empty one is [0]."""
+    nodes, ptr, feats = (np.ascontiguousarray(a, np.int32).ravel() for a in fv)
+    return nodes, (ptr if len(ptr) else np.zeros(1, np.int32)), feats
+
+
+def search_for_triangulation_batch(kf1, kf2s, has_mp1, fv1, has_mp2s, fv2s, F12s, epipoles, level_sigma2,
+                                   scale_factors, only_stereo=False, check_ori=True):
+    """SearchForTriangulation (ORBmatcher.cc:597-746) of keyframe kf1 against every neighbour of kf2s in one call
+    (LocalMapping::CreateNewMapPoints).  has_mp*: GetMapPoint(i) != NULL; fv* = (nodes, ptr, feats) node-sorted CSR
+    FeatureVectors; F12s [n_nb, 3, 3]; epipoles [n_nb, 2] = (ex, ey) of :603-609.
+    -> (matches12 int32[n_nb, kf1.n]: KF2 index or -1, nmatches int32[n_nb])."""
+    n_nb = len(kf2s)
+    hm1 = np.ascontiguousarray(has_mp1, np.uint8)
+    n1, p1, f1 = _fv(fv1)
+    hm2 = [np.ascontiguousarray(a, np.uint8).ravel() for a in has_mp2s]
+    fvs = [_fv(fv) for fv in fv2s]
+    if not (len(hm2) == len(fvs) == n_nb):
+        raise ValueError("one has_mp2 and one FeatureVector per neighbour")
+    cat = lambda xs, dt: np.concatenate([np.zeros(0, dt)] + list(xs)).astype(dt)  # noqa: E731
+    mp2_ptr = np.concatenate([[0], np.cumsum([len(a) for a in hm2])]).astype(np.int32)
+    fv2_ptr = np.concatenate([[0], np.cumsum([len(n) for n, _, _ in fvs])]).astype(np.int32)
+    feat_off = np.concatenate([[0], np.cumsum([len(f) for _, _, f in fvs])]).astype(np.int64)
+    ptr2 = cat([[0]] + [p[1:len(n) + 1] + feat_off[k] for k, (n, p, _) in enumerate(fvs)], np.int32)
+    nodes2, feats2 = cat([n for n, _, _ in fvs], np.int32), cat([f for _, _, f in fvs], np.int32)
+    hm2c = cat(hm2, np.uint8)
+    F = np.ascontiguousarray(F12s, np.float32).reshape(n_nb, 9)
+    ep = np.ascontiguousarray(epipoles, np.float32).reshape(n_nb, 2)
+    sig, sc = np.ascontiguousarray(level_sigma2, np.float32), np.ascontiguousarray(scale_factors, np.float32)
+    if len(sig) != len(sc):
+        raise ValueError("level_sigma2 and scale_factors differ in length")
+    hs = (C.c_void_p * max(n_nb, 1))(*[f.h.value for f in kf2s])
+    m12 = np.full((n_nb, kf1.n), -2, np.int32)  # -2: not written (an error return leaves the outputs alone)
+    nm = np.full(n_nb, -2, np.int32)
+    _check(lib().ygzfe_search_for_triangulation_batch(
+        kf1.h, _p(hm1), len(n1), _p(n1), _p(p1), _p(f1), n_nb, hs, _p(mp2_ptr), _p(hm2c), _p(fv2_ptr), _p(nodes2),
+        _p(ptr2), _p(feats2), _p(F), _p(ep), _p(sig), _p(sc), len(sig), int(only_stereo), int(check_ori), _p(m12),
+        _p(nm)), "search_for_triangulation_batch")
+    return m12, nm
+
+
+def search_for_triangulation(kf1, kf2, has_mp1, fv1, has_mp2, fv2, F12, epipole, level_sigma2, scale_factors,
+                             only_stereo=False, check_ori=True):
+    """SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo) (ORBmatcher.cc:597-746) for one neighbour
+    -> (matches12 int32[kf1.n]: KF2 index or -1, nmatches)."""
+    hm1, hm2 = np.ascontiguousarray(has_mp1, np.uint8), np.ascontiguousarray(has_mp2, np.uint8)
+    n1, p1, f1 = _fv(fv1)
+    n2, p2, f2 = _fv(fv2)
+    F, ep = np.ascontiguousarray(F12, np.float32).reshape(9), np.ascontiguousarray(epipole, np.float32).reshape(2)
+    sig, sc = np.ascontiguousarray(level_sigma2, np.float32), np.ascontiguousarray(scale_factors, np.float32)
+    if len(sig) != len(sc):
+        raise ValueError("level_sigma2 and scale_factors differ in length")
+    m12 = np.full(kf1.n, -2, np.int32)
+    nm = np.full(1, -2, np.int32)
+    _check(lib().ygzfe_search_for_triangulation(
+        kf1.h, _p(hm1), len(n1), _p(n1), _p(p1), _p(f1), kf2.h, _p(hm2), len(n2), _p(n2), _p(p2), _p(f2), _p(F), _p(ep),
+        _p(sig), _p(sc), len(sig), int(only_stereo), int(check_ori), _p(m12), _p(nm)), "search_for_triangulation")
+    return m12, int(nm[0])
+
+
 class SparseImgAlign:
     """SparseImgAlign(n_levels, min_level, n_iter=10, method=GaussNewton) (SparseImageAlign.h:37-60)."""
     GaussNewton, LevenbergMarquardt = 0, 1  # NLLSSolver's methods (NLSSolver.h:40-43)
