@@ -573,6 +573,21 @@ def align2d_batch(cur_frame, level, patches_with_border, patches, px, n_iter=10)
     return conv.astype(bool), px
 
 
+def align2d_image(img, patch_with_border, patch, px, n_iter=10, device=0):
+    """Align2D(const cv::Mat &cur_img, ...) (Align.cc:8-105) on a host image, whose rows may be
+    `img.strides[0]` > width bytes apart -> (converged, px float32[2])."""
+    img = np.asarray(img)
+    if img.dtype != np.uint8 or img.ndim != 2 or img.strides[1] != 1 or img.strides[0] < img.shape[1]:
+        img = np.ascontiguousarray(img, np.uint8)
+    pwb = np.ascontiguousarray(patch_with_border, np.uint8).reshape(100)
+    p = np.ascontiguousarray(patch, np.uint8).reshape(64)
+    px = np.array(px, np.float32).reshape(2)
+    conv = np.zeros(1, np.uint8)
+    _check(lib().ygzfe_align2d_image(device, _p(img), img.shape[1], img.shape[0], img.strides[0], _p(pwb), _p(p),
+                                     n_iter, _p(px), _p(conv)), "align2d_image")
+    return bool(conv[0]), px
+
+
 def find_direct_projection_batch(ref_frames, cur_frame, cam, ref_index, kp_ref, pt_ref, T_cr, px):
     refs = (C.c_void_p * len(ref_frames))(*[f.h.value for f in ref_frames])
     ref_index = np.ascontiguousarray(ref_index, np.int32)

@@ -327,3 +327,82 @@ def test_search_direct_items_own_tcr(gpu):
     assert np.array_equal(m, om) and np.array_equal(px, opx)
     base, bm = gpu.search_direct_batch(kf_fr, cur_fr, cam, *(args[:4] + (d["T_cr"], args[5])))
     assert not np.array_equal(base, px)  # the per-item poses were used
+
+
+# ---------------------------------------------------------------- Align2D beyond level 0 of one frame
+def edge_guesses(w, h):
+    """Guesses whose floor is on the first-out / first-in columns and rows (3, 4, w - 5, w - 4 and the
+    same for rows; Align.cc:56-59) -> (guesses float32[8, 2], whether the first iteration breaks)."""
+    g = [(c + 0.5, h // 2 + 0.25) for c in (3, 4, w - 5, w - 4)] + [(w // 2 + 0.25, r + 0.5) for r in (3, 4, h - 5, h - 4)]
+    return np.array(g, np.float32), np.array([True, False, False, True] * 2)
+
+
+@pytest.mark.parametrize("level", [1, 3, 5])
+def test_align2d_coarse_levels_bitexact(gpu, level):
+    """align2d_batch (k_align2d) on levels 1, 3 and 5 of a 641x479 / x1.2 pyramid (odd widths), n around
+    the 256-lane block, n_iter 0 .. 30, guesses on the border columns and rows, one flat patch."""
+    W, H, sf, nl = 641, 479, 1.2, 8
+    img = S.frame(12, W, H)
+    fr = gpu.ORBextractor(1000, sf, nl, 20, 7).ComputePyramid(img)
+    lv = O.OrbOracle(1000, sf, nl, 20, 7).pyramid(img)[level]
+    h, w = lv.shape
+    assert np.array_equal(fr.level(level), lv)
+    rng = np.random.default_rng(level)
+    pts = np.stack([rng.integers(12, w - 12, 257), rng.integers(12, h - 12, 257)], 1)
+    pwb, p = patches_around(lv, pts, rng)
+    guess = (pts + rng.uniform(-2.5, 2.5, pts.shape)).astype(np.float32)
+    eg, breaks = edge_guesses(w, h)
+    guess[1:9] = eg
+    pwb[9], p[9] = 90, 90          # a flat patch: H is singular, the first update is NaN
+    for n_iter in (0, 1, 10, 30):
+        want = [O.align2d(lv, pwb[i], p[i], guess[i], n_iter) for i in range(257)]
+        ook = np.array([r[0] for r in want])
+        opx = np.array([r[1] for r in want], np.float32)
+        nan = np.isnan(opx).any(1)
+        assert np.array_equal(np.nonzero(nan)[0], [9] if n_iter else [])
+        for n in (1, 255, 256, 257):
+            conv, px = gpu.align2d_batch(fr, level, pwb[:n], p[:n], guess[:n], n_iter)
+            assert np.array_equal(conv, ook[:n]), (n_iter, n)
+            keep = ~nan[:n]
+            assert np.array_equal(px[keep].view(np.uint32), opx[:n][keep].view(np.uint32)), (n_iter, n)
+            assert np.array_equal(px[~keep], opx[:n][~keep], equal_nan=True) and not conv[~keep].any()
+        moved = (opx[1:9] != guess[1:9]).any(1)
+        assert np.array_equal(moved, ~breaks if n_iter else np.zeros(8, bool)), n_iter
+        assert not ook[1:9][breaks].any()
+        if n_iter == 0:
+            assert not ook.any() and np.array_equal(opx, guess)
+    assert ook.mean() > 0.5
+
+
+def test_align2d_image_bitexact(gpu):
+    """ygzfe_align2d_image (k_align2d_window) on a host image with stride > width against ygzo_align2d:
+    guesses within 24 px of every corner and edge (the 48x48 window is clipped), trajectories that leave
+    the window inside the image (the second pass on the whole image; tests/test_cpu_direct_views.py
+    asserts that they do) and one that leaves the image."""
+    import _direct_views as V
+    img = V.host_image()
+    h, w = img.shape
+    assert img.strides[0] > w
+    dense = np.ascontiguousarray(img)
+    rng = np.random.default_rng(3)
+    near = [(10, 10), (w - 11, 10), (10, h - 11), (w - 11, h - 11), (w // 2, 9), (w // 2, h - 10), (8, h // 2),
+            (w - 9, h // 2), (23, 23), (w - 24, h - 24), (300, 200), (500, 90)]
+    pts = np.array(near)
+    pwb, p = patches_around(img, pts, rng)
+    cases = [(pwb[i], p[i], (pts[i] + rng.uniform(-0.8, 0.8, 2)).astype(np.float32)) for i in range(len(pts))]
+    eg, breaks = edge_guesses(w, h)
+    cases += [(pwb[10], p[10], g) for g in eg]                       # the image's own border rule
+    cases += [(pwb[10], p[10], np.array(g, np.float32)) for g in ((-10, 5), (w + 3, h + 3), (0.5, 0.5))]
+    walks = [V.walk_case(s) for s in V.WALK_OUT_SEEDS] + [V.walk_case(s, edge=True) for s in V.OUT_OF_IMAGE_SEEDS]
+    cases += [(b.reshape(-1), np.ascontiguousarray(b[1:9, 1:9]).reshape(-1), g) for b, g in walks]
+    n_conv = 0
+    for k, (b, q, g) in enumerate(cases):
+        for n_iter in ((10,) if k else (0, 1, 10)):
+            ok, px = O.align2d(dense, b, q, g, n_iter)
+            gok, gpx = gpu.align2d_image(img, b, q, g, n_iter)
+            assert gok == ok, (k, n_iter)
+            assert np.array_equal(gpx.view(np.uint32), px.view(np.uint32)), (k, n_iter, gpx, px)
+        n_conv += ok
+    assert n_conv >= 8
+    far = [np.abs(O.align2d(dense, b, q, g)[1] - g).max() for b, q, g in cases[-len(walks):][:len(V.WALK_OUT_SEEDS)]]
+    assert min(far) > 15, far   # the walk-out cases did travel
