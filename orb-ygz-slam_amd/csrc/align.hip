@@ -1496,6 +1496,37 @@ hipError_t launch_sparse_align(const AlignLevels &lv, const ygzfe_camera &cam, c
     return hipGetLastError();
 }
 
+// the batch's align jobs, one per (ref, cur) pair of its frames
+__global__ void k_build_align_jobs(AlignJob *jobs, int n_pairs, const int32_t *ref_idx, const int32_t *cur_idx,
+                                   const uint8_t *pyr, uint32_t pitch, const ygzfe_kp *kps, const int32_t *counts,
+                                   int kp_cap, const float *xyz, const uint8_t *usable, int max_level, int min_level,
+                                   const ygzfe_se3 *T_init) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_pairs) return;
+    const int r = ref_idx[p], c = cur_idx[p];
+    AlignJob j;
+    j.ref_pyr = pyr + (size_t)r * pitch;
+    j.cur_pyr = pyr + (size_t)c * pitch;
+    j.kps = kps + (size_t)r * kp_cap;
+    j.xyz = xyz + (size_t)p * kp_cap * 3;
+    j.usable = usable + (size_t)p * kp_cap;
+    j.n = counts[r];
+    j.max_level = max_level;
+    j.min_level = min_level;
+    j.method = 0;
+    j.T_init = T_init[p];
+    jobs[p] = j;
+}
+
+hipError_t launch_build_align_jobs(AlignJob *jobs, int n_pairs, const int32_t *ref_idx, const int32_t *cur_idx,
+                                   const uint8_t *pyr, uint32_t pitch, const ygzfe_kp *kps, const int32_t *counts,
+                                   int kp_cap, const float *xyz, const uint8_t *usable, int max_level, int min_level,
+                                   const ygzfe_se3 *T_init, hipStream_t st) {
+    hipLaunchKernelGGL(k_build_align_jobs, dim3((n_pairs + 63) / 64), dim3(64), 0, st, jobs, n_pairs, ref_idx, cur_idx,
+                       pyr, pitch, kps, counts, kp_cap, xyz, usable, max_level, min_level, T_init);
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------ Align2D
 __device__ void inverse3(const float m[9], float r[9]) {
 #define M(i, j) m[(i) * 3 + (j)]

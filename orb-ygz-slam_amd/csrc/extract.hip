@@ -1853,7 +1853,7 @@ __device__ __forceinline__ void body_list(const Plan *__restrict__ plan, const L
 
 }  // namespace oct
 
-// Work queues between the octree sort stages of one node-pool class (api.cpp zeroes
+// Work queues between the octree sort stages of one node-pool class (the host zeroes
 // the counters before each extraction): a task (f << 4 | l) whose level has more
 // candidates than a stage's LDS holds is appended to the next stage's list.
 struct OctQueue {
@@ -2441,7 +2441,7 @@ static int device_cus() {
     return n;
 }
 
-// Arithmetic guard, run once per device before the first call (api.cpp
+// Arithmetic guard, run once per device before the first call (host.cpp
 // ensure_device): the two bit-level tricks the kernels rest on, evaluated with this
 // translation unit's own flags and helpers, so a build or mode change that breaks them
 // (fast-math, f16 denormal flushing, a rounding mode other than nearest-even) fails

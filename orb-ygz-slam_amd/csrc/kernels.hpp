@@ -143,6 +143,11 @@ struct AlignJob {
 hipError_t launch_sparse_align(const AlignLevels &lv, const ygzfe_camera &cam, const AlignJob *jobs,
                                int njobs, float *scratch, size_t scratch_per_job, ygzfe_align_result *out,
                                hipStream_t st, int max_n, int method = 0);
+// jobs[p] for the pair (ref_idx[p], cur_idx[p]) of a batch's frames (pyramids `pitch` bytes apart)
+hipError_t launch_build_align_jobs(AlignJob *jobs, int n_pairs, const int32_t *ref_idx, const int32_t *cur_idx,
+                                   const uint8_t *pyr, uint32_t pitch, const ygzfe_kp *kps, const int32_t *counts,
+                                   int kp_cap, const float *xyz, const uint8_t *usable, int max_level, int min_level,
+                                   const ygzfe_se3 *T_init, hipStream_t st);
 size_t sparse_align_scratch_floats(int n);
 int sparse_align_reg_capacity();  // features the register kernel holds (one per feature-wave thread)
 // stream placement probe (ensure_align_stream): a kernel that holds its stream for

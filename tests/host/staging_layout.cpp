@@ -1,7 +1,7 @@
 // BlockLayout / at<T>() of csrc/staging.hpp, without a GPU: built with
 // -fsanitize=address,undefined and run by tests/test_cpu_staging.py.
 //
-// 1. the layouts of the host entry points of api.cpp, replayed take by take for a few
+// 1. the layouts of the host entry points of csrc/api_*.cpp, replayed take by take for a few
 //    inputs, against offsets worked out by hand from the aligned sums these entry
 //    points were first written with (a16(x) = x rounded up to 16, a256 to 256; the hand
 //    sum stands in the comment beside each number, none is computed through the helper);

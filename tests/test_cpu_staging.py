@@ -1,7 +1,7 @@
 """csrc/staging.hpp (the packed-block layout helper of the host layer) without a GPU.
 
 tests/host/staging_layout.cpp is a stand-alone program that includes only that header:
-the layouts of api.cpp's host entry points against offsets worked out by hand, the
+the layouts of the api_*.cpp host entry points against offsets worked out by hand, the
 properties of any sequence of takes, and every part of an exactly sized block written and
 read back.  It is built with AddressSanitizer and UBSan and run as a child process.
 """

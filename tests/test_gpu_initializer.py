@@ -135,7 +135,7 @@ def test_round5_repro_order_with_graphs(gpu):
 @pytest.mark.parametrize("cfg", ["INI", "C2"])
 def test_batch_extract_captured_in_a_graph(gpu, cfg):
     """the batch path forks the octree's node-pool classes after the
-    first onto the batch's aux streams (api.cpp ygzfe_batch_extract_split -> launch_octree),
+    first onto the batch's aux streams (api_batch.cpp ygzfe_batch_extract_split -> launch_octree),
     and `bench.py --graph 1` captures that path into a HIP graph.  The initialiser's 2048-node
     level-0 class makes two launch groups, so a fork and join happen inside the capture.
     Captured on a torch stream, replayed twice, then new frames uploaded into the same

@@ -2,7 +2,7 @@
 with synthetic descriptors, bit for bit against the oracle's hamming_best2.
 
 Batch.bind(desc=, counts=) lets a test write descriptors and per-frame counts straight into device
-buffers; ygzfe_batch_match reads exactly those bound buffers (csrc/api.cpp: b->ws.desc / b->ws.counts),
+buffers; ygzfe_batch_match reads exactly those bound buffers (csrc/api_hamming.cpp: b->ws.desc / b->ws.counts),
 so no extraction is needed.  Covered here and nowhere else in the suite:
 
 * frames with 0 rows as train and as query, counts either side of the 32-query group, the 64-lane
