@@ -100,6 +100,26 @@ int ygzfe_extractor_dso_grid(ygzfe_extractor *ex, int32_t *get, const int32_t *s
 int ygzfe_orb_plan(const ygzfe_orb_params *p, int width, int height, int32_t *level_w, int32_t *level_h,
                    int32_t *budget, int32_t *ncells, int32_t *umax);
 
+/* Host-only (no device touched): what the kernel launchers choose from that plan, asked of
+ * the functions that choose at launch time.  per_level holds nlevels rows of
+ * YGZFE_PLAN_LEVEL_FIELDS values:
+ *   0 n_ini    initial octree nodes (DistributeOctTree, ORBextractor.cc:537-539; at least 1)
+ *   1 oct_rb   bits of the root-column field of the octree path codes
+ *   2 ncells   FAST cells
+ *   3 fast_rw, 4 fast_rh   largest cell ROI width / height (0 without cells)
+ *   5 the octree node-pool class: 256, 512, 1024 or 2048
+ *   6 S, 7 R   the FAST cell kernel instance of the level's own launch, as the batched
+ *              extraction launches it (0, 0 without cells: no launch)
+ *   8, 9       keys the first octree sort stage holds for the level in the batched and in the
+ *              single-frame extraction (1024, 4096 or 8192); a (frame, level) with more
+ *              candidates moves on to the later stages
+ * per_plan holds YGZFE_PLAN_FIELDS values: 0 S, 1 R of the one FAST launch over every level's
+ * cells (single-frame extraction; 0, 0 without cells), 2 the number of octree launch groups
+ * (runs of consecutive levels of one node-pool class).  Either pointer may be NULL. */
+#define YGZFE_PLAN_LEVEL_FIELDS 10
+#define YGZFE_PLAN_FIELDS 3
+int ygzfe_orb_plan_choices(const ygzfe_orb_params *p, int width, int height, int32_t *per_level, int32_t *per_plan);
+
 int ygzfe_frame_create(ygzfe_extractor *ex, int width, int height, ygzfe_frame **out);
 void ygzfe_frame_destroy(ygzfe_frame *f);
 /* Frame::ComputeImagePyramid -> ORBextractor::ComputePyramid

@@ -98,6 +98,32 @@ int ygzfe_orb_plan(const ygzfe_orb_params *p, int width, int height, int32_t *le
     return YGZFE_OK;
 }
 
+int ygzfe_orb_plan_choices(const ygzfe_orb_params *p, int width, int height, int32_t *per_level, int32_t *per_plan) {
+    if (!p) { set_error("null argument"); return YGZFE_EINVAL; }
+    PlanHost ph;
+    char err[256];
+    if (build_plan(*p, width, height, &ph, err, sizeof(err)) != 0) { set_error("%s", err); return YGZFE_EINVAL; }
+    const Plan &P = ph.plan;
+    for (int l = 0; l < P.nlevels && per_level; l++) {
+        const LevelDesc &L = P.lv[l];
+        int32_t *o = per_level + (size_t)l * YGZFE_PLAN_LEVEL_FIELDS;
+        int S = 0, R = 0;
+        if (L.ncells > 0) fast_shape_pick(L.fast_rw, L.fast_rh, S, R);  // launch_fast skips a level without cells
+        const int nc = octree_nc(L);
+        const int32_t row[YGZFE_PLAN_LEVEL_FIELDS] = {L.n_ini, L.oct_rb, L.ncells, L.fast_rw, L.fast_rh, nc, S, R,
+                                                      octree_sort0_keys(nc, false), octree_sort0_keys(nc, true)};
+        memcpy(o, row, sizeof(row));
+    }
+    if (per_plan) {
+        int S = 0, R = 0;
+        if (P.ncells > 0) fast_shape_merged(P, S, R);
+        per_plan[0] = S;
+        per_plan[1] = R;
+        per_plan[2] = octree_groups(P);
+    }
+    return YGZFE_OK;
+}
+
 int ygzfe_extractor_levels(const ygzfe_extractor *ex, int *nlevels, float *scale, float *inv_scale,
                            float *sigma2, float *inv_sigma2) {
     if (!ex) { set_error("null extractor"); return YGZFE_EINVAL; }

@@ -2563,11 +2563,13 @@ hipError_t launch_blur_rest(const uint8_t *pyr, uint8_t *blur, uint32_t pitch, c
 }
 
 // the (S, R) instance of the per-cell slice for ROIs up to rw x rh
-static void fast_shape_pick(int rw, int rh, int &S, int &R) {
+void fast_shape_pick(int rw, int rh, int &S, int &R) {
     fast_slice_shape(rw, rh, S, R);
     if (S == 36 && R > 40) S = 40;
     if (!((S == 36 && R == 40) || (S == 40 && R <= 56))) S = R = std::max(S, R);
 }
+// (72, 72) is instantiated but unreachable: no level size yields a ROI side above 59, a lone cell
+// clipped to the border (tests/test_cpu_plan_sweep.py, level sizes 62..400; larger levels have smaller cells)
 #define YGZ_FAST_SHAPES(X) X(36, 40) X(40, 40) X(40, 48) X(40, 56) X(48, 48) X(56, 56) X(64, 64) X(72, 72)
 
 hipError_t launch_fast(const uint8_t *pyr, uint32_t pitch, const Plan &hp, const Plan *dp, const CellDesc *dcells,
@@ -2604,21 +2606,27 @@ hipError_t launch_fast(const uint8_t *pyr, uint32_t pitch, const Plan &hp, const
     return hipGetLastError();
 }
 
-// Every level's cells in ONE launch (the single-frame path: one frame's cells fill
-// the GPU anyway, and three dependent launches cost three dispatch gaps): the
-// slices of the largest ROI of any level.
-hipError_t launch_fast_merged(const uint8_t *pyr, uint32_t pitch, const Plan &hp, const Plan *dp,
-                              const CellDesc *dcells, uint32_t *cellbuf, int *cellcnt, int nframes, hipStream_t st,
-                              int *clear_flag) {
-    if (hp.ncells == 0) return hipSuccess;
+// the instance of the merged launch: the largest ROI width and height of any level with cells
+void fast_shape_merged(const Plan &hp, int &S, int &R) {
     int rw = 0, rh = 0;
     for (int l = 0; l < hp.nlevels; l++) {
         if (hp.lv[l].ncells == 0) continue;
         rw = std::max(rw, hp.lv[l].fast_rw);
         rh = std::max(rh, hp.lv[l].fast_rh);
     }
-    int S, R;
     fast_shape_pick(rw, rh, S, R);
+}
+
+// Every level's cells in ONE launch (the single-frame path: one frame's cells fill
+// the GPU anyway, and three dependent launches cost three dispatch gaps): the
+// slices of the largest ROI of any level.
+hipError_t launch_fast_merged(const uint8_t *pyr, uint32_t pitch, const Plan &hp, const Plan *dp,
+                              const CellDesc *dcells, uint32_t *cellbuf, int *cellcnt, int nframes, hipStream_t st,
+                              int *clear_flag) {
+    if (hp.ncells == 0)  // no kernel to clear the flag: a plan without any cell (every level under 62 px a side)
+        return clear_flag ? hipMemsetAsync(clear_flag, 0, sizeof(int), st) : hipSuccess;
+    int S, R;
+    fast_shape_merged(hp, S, R);
     const size_t lds = kFastWaves * (size_t)fast_slice_bytes(S, R);
     const dim3 grid((hp.ncells + kFastWaves - 1) / kFastWaves, nframes);
 #define YGZ_FAST(SS, RR)                                                                                        \
@@ -2631,10 +2639,13 @@ hipError_t launch_fast_merged(const uint8_t *pyr, uint32_t pitch, const Plan &hp
 }
 
 // node pool per level: budget + 4 nIni + 16 (plan.cpp), rounded up to a power of two
-static int octree_nc(const LevelDesc &L) {
+int octree_nc(const LevelDesc &L) {
     const int need = L.budget + 4 * L.n_ini + 16;
     return need <= 256 ? 256 : need <= 512 ? 512 : need <= 1024 ? 1024 : 2048;
 }
+// keys the first sort stage (k_octree_sort) of a level of class nc holds in LDS; wide = the
+// single-frame path.  launch_octree_levels refuses to launch an instance that disagrees.
+int octree_sort0_keys(int nc, bool wide) { return wide && nc <= 1024 ? 8192 : nc <= 256 ? 1024 : 4096; }
 
 // threads per workgroup of the larger octree classes: the workgroup holds its
 // LDS (two per CU) through a chain of barrier-separated passes, so more waves
@@ -2651,7 +2662,7 @@ constexpr int kOctListThreads = YGZ_OCT_LIST_THREADS;
 // launch groups: runs of consecutive levels with one node-pool class (the class
 // sequence can go back up, e.g. when the last level's remainder budget or a flipped
 // n_ini moves it, so a plan may hold up to nlevels groups)
-static int octree_groups(const Plan &hp) {
+int octree_groups(const Plan &hp) {
     int G = 0;
     for (int l = 0; l < hp.nlevels; G++) {
         const int nc = octree_nc(hp.lv[l]);
@@ -2687,6 +2698,7 @@ static hipError_t launch_octree_levels(int nc, const Plan *dp, const uint32_t *c
     const OctQueue q3{cq + 4, cq + 5, lists + 2 * T, nullptr, nullptr};
     const int tasks = nframes * nl;
 #define YGZ_OCT_SORT0(NC, NK, NT)                                                                                 \
+    if (NK != octree_sort0_keys(nc, wide)) return hipErrorInvalidValue;                                           \
     hipLaunchKernelGGL((k_octree_sort<NC, NK, NT>), grid, dim3(NT), 0, st, dp, cellbuf, cellcnt, candA, candB, hdr, \
                        l0, q0)
 #define YGZ_OCT_REST(NC, Q1)                                                                                      \

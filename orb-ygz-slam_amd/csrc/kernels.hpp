@@ -30,6 +30,15 @@ hipError_t launch_octree(const Plan &hp, const Plan *dp, const uint32_t *cellbuf
                          int nframes, hipStream_t st, const hipStream_t *side = nullptr, int nside = 0,
                          hipEvent_t fork = nullptr, const hipEvent_t *join = nullptr, bool wide = false);
 size_t octree_queue_ints(const Plan &hp, int nframes);
+// What the launchers above choose from a plan (host only; ygzfe_orb_plan_choices reports them):
+// the k_fast_cells<S, R> instance for ROIs up to rw x rh (launch_fast: a level's fast_rw x fast_rh)
+// and of launch_fast_merged; a level's node-pool class; the LDS key capacity of the first octree
+// sort stage of a class (wide = the single-frame path); launch_octree's launch groups
+void fast_shape_pick(int rw, int rh, int &S, int &R);
+void fast_shape_merged(const Plan &hp, int &S, int &R);
+int octree_nc(const LevelDesc &L);
+int octree_sort0_keys(int nc, bool wide);
+int octree_groups(const Plan &hp);
 // keypoint rows + per-row orientation jobs (uint2 per selection slot: centre byte offset, w | level << 16)
 hipError_t launch_emit_kps(const Plan &hp, const Plan *dp, const uint32_t *sel, const int *selcnt,
                            const int *n_existing, ygzfe_kp *kps, int *counts, int row_cap, uint2 *ojobs, int nframes,

@@ -224,16 +224,26 @@ int build_plan(const ygzfe_orb_params &p, int W, int H, PlanHost *ph, char *err,
             }
         }
         L.ncells = (int)ph->cells.size() - L.cell_begin;
-        // DistributeOctTree initial nodes (ORBextractor.cc:537-539)
-        int nIni = (int)roundf((float)(maxBX - minB) / (maxBY - minB));
+        // DistributeOctTree initial nodes (ORBextractor.cc:537-539).  A level no larger than
+        // its border in either direction has no candidate area (and no cells above): one
+        // root, a finite hX and empty code tables, with nothing divided by its zero extent
+        const bool has_area = maxBX - minB > 0 && maxBY - minB > 0;
+        int nIni = has_area ? (int)roundf((float)(maxBX - minB) / (maxBY - minB)) : 1;
         if (nIni < 1) nIni = 1;
         if (nIni > 8) {
             snprintf(err, errlen, "level %d aspect ratio needs %d initial octree nodes (max 8)", l, nIni);
             return -1;
         }
         L.n_ini = nIni;
-        L.hX = (float)(maxBX - minB) / nIni;
-        octree_code_tables(L, &ph->tabs);
+        if (has_area) {
+            L.hX = (float)(maxBX - minB) / nIni;
+            octree_code_tables(L, &ph->tabs);
+        } else {
+            L.hX = 1.f;
+            L.oct_rb = 0;
+            L.oct_dn = 3;  // as a one-pixel extent: the list phase (no key: one pass) must stay below it
+            L.oct_xtab = L.oct_ytab = (int)ph->tabs.size();
+        }
         L.sel_cap = std::max(L.budget + 4, 4 * nIni + 4) + 8;
         L.sel_off = sel_total;
         sel_total += L.sel_cap;

@@ -125,6 +125,24 @@ def orb_plan(nfeatures, scale_factor, nlevels, ini_th=20, min_th=7, width=752, h
             "umax": um.tolist()}
 
 
+PLAN_LEVEL_FIELDS = ("n_ini", "oct_rb", "ncells", "fast_rw", "fast_rh", "node_class", "fast_S", "fast_R",
+                     "sort0_keys_batch", "sort0_keys_single")
+
+
+def orb_plan_choices(nfeatures, scale_factor, nlevels, ini_th=20, min_th=7, width=752, height=480, blur=BLUR_CV4):
+    """Host-only (ygzfe_orb_plan_choices): what the launchers choose from the plan.  "levels": one dict of
+    PLAN_LEVEL_FIELDS per level, plus "fast" = (S, R) of the level's own FAST launch (None without cells);
+    "merged_fast": (S, R) of the single-frame path's one FAST launch (None without cells); "octree_groups"."""
+    p = OrbParams(nfeatures, scale_factor, nlevels, ini_th, min_th, blur)
+    lv = np.zeros((nlevels, len(PLAN_LEVEL_FIELDS)), np.int32)
+    pl = np.zeros(3, np.int32)
+    _check(lib().ygzfe_orb_plan_choices(C.byref(p), width, height, _p(lv), _p(pl)), "orb_plan_choices")
+    levels = [dict(zip(PLAN_LEVEL_FIELDS, row)) for row in lv.tolist()]
+    for d in levels:
+        d["fast"] = (d["fast_S"], d["fast_R"]) if d["ncells"] else None
+    return {"levels": levels, "merged_fast": (int(pl[0]), int(pl[1])) if pl[0] else None, "octree_groups": int(pl[2])}
+
+
 def _created(what, *args):
     """The handle that ygzfe_<what>(*args, &handle) makes."""
     h = C.c_void_p()

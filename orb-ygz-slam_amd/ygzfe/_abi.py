@@ -12,8 +12,8 @@ KINDS = {"p": C.c_void_p, "s": C.c_char_p, "i": C.c_int, "f": C.c_float, "z": C.
 
 YGZFE = """
     last_error=s: device_count=i: extractor_create=i:pip extractor_destroy=v:p extractor_levels=i:pppppp
-    extractor_features_per_level=i:pp extractor_dso_grid=i:ppp orb_plan=i:piippppp frame_create=i:piip
-    frame_destroy=v:p compute_pyramid=i:pppi compute_pyramid_device=i:pppip frame_level=i:pipppi frame_set_level=i:pipi
+    extractor_features_per_level=i:pp extractor_dso_grid=i:ppp orb_plan=i:piippppp orb_plan_choices=i:piipp
+    frame_create=i:piip frame_destroy=v:p compute_pyramid=i:pppi compute_pyramid_device=i:pppip frame_level=i:pipppi frame_set_level=i:pipi
     frame_levels=i:piipp frame_set_levels=i:piipp extract=i:ppipiipp detect_and_compute=i:pppipipp
     batch_create=i:piiiip batch_destroy=v:p batch_info=i:pppp batch_frames=i:pp batch_bind_buffers=i:ppppp
     batch_upload=i:ppi batch_extract=i:pip batch_extract_split=i:pipp batch_check=i:p batch_match=i:pipppppp

@@ -55,6 +55,34 @@ def test_plan_tables(ygzfe, cfg):
     assert plan["umax"] == orc.umax
 
 
+GRID_SIZES = [(640, 480), (641, 479), (752, 480), (1280, 720), (97, 61), (255, 257), (333, 111), (64, 200), (480, 96),
+              (62, 89), (1919, 1079)]
+GRID_PARAMS = [(500, 1.2, 8), (2000, 1.2, 8), (1000, 2.0, 4), (300, 1.05, 16), (777, 1.5, 4), (1, 1.3, 5), (0, 1.2, 3),
+               (150, 1.7, 1), (2000, 1.1, 16), (31, 1.44, 7), (1000, 2.5, 2)]
+
+
+@pytest.mark.parametrize("W,H", GRID_SIZES)
+def test_plan_sizes_and_budgets_match_the_oracle(ygzfe, W, H):
+    """Level sizes (cvRound of W, H times the float inverse scale, ORBextractor.cc:1131-1132) and budgets
+    (:434-445) of the library's plan against the oracle's, at odd sizes, scale factors beyond the three
+    benchmark configurations, and 1 and 16 levels.  A plan the library refuses (a level under 1 px, or one
+    needing more than 8 root columns) is refused for that stated reason."""
+    compared = 0
+    for nf, sf, nl in GRID_PARAMS:
+        orc = O.OrbOracle(nf, sf, nl, 20, 7)
+        sizes = orc.level_sizes(W, H)
+        try:
+            plan = ygzfe.orb_plan(nf, sf, nl, 20, 7, W, H)
+        except ygzfe.YgzfeError as e:
+            assert min(min(s) for s in sizes) < 1 or "initial octree nodes" in str(e), (W, H, nf, sf, nl, str(e))
+            continue
+        assert plan["sizes"] == sizes, (W, H, nf, sf, nl)
+        assert plan["budget"] == orc.feat_per_level, (W, H, nf, sf, nl)
+        assert plan["umax"] == orc.umax
+        compared += 1
+    assert compared >= (1 if W > 3 * H else 4), compared  # the wide sizes pass 8 root columns at most level counts
+
+
 def test_cell_grid_c2(ygzfe):
     """C2 level 0 has 14x24 cells; level 3 (94x60) has none (nRows = int(28/30) = 0)."""
     plan = ygzfe.orb_plan(1000, 2.0, 4, 20, 7, 752, 480)

@@ -178,6 +178,7 @@ def test_batch_blur_every_pixel(gpu, size, cfg, blur):
     b = gpu.Batch((nf, sf, nl, ini, mn, blur), 0, W, H, 2)
     b.upload(frames)
     b.extract(len(frames))
+    b.check()
     for i in range(len(frames)):
         for l in range(b.nlevels):
             lv = b.read_level(i, l)
