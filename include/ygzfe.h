@@ -373,6 +373,66 @@ int ygzfe_search_for_triangulation(ygzfe_match_frame *kf1, const uint8_t *has_mp
                                    const float *level_sigma2, const float *scale_factors, int n_levels,
                                    int only_stereo, int check_ori, int32_t *matches12, int32_t *nmatches);
 
+/* MapPoint::PredictScale (MapPoint.cc:343-357) as a table, host only (libm's logf, no device):
+ * n_levels - 1 thresholds, thr[L-1] = the smallest positive finite float r with
+ * ceil(logf(r) / log_scale_factor) >= L, L = 1 .. n_levels-1 (+inf where no finite r reaches L).
+ * PredictScale(ratio) clamped to [0, n_levels-1] is then the number of thresholds <= ratio,
+ * wherever logf is monotone.  n_levels in [1, 16], log_scale_factor finite and positive. */
+int ygzfe_predict_scale_thresholds(float log_scale_factor, int n_levels, float *thr);
+
+/* The search of ORBmatcher::Fuse(pKF, vpMapPoints, th) (ORBmatcher.cc:748-866) for every pair of
+ * n_kf keyframes and n_pts map points at once (LocalMapping::SearchInNeighbors,
+ * LocalMapping.cc:1228-1326: all targets of the forward phase in one call; the backward phase is
+ * n_kf = 1): one packed upload, one launch, one download and one synchronisation per call.  The map
+ * surgery that follows the search (:868-882: Replace, AddObservation, AddMapPoint) is the caller's:
+ * it needs only best_idx / best_dist per pair and replays them in the reference's order.
+ *
+ * Inputs.  kf[k]: a match frame (keypoints, descriptors, u_right, bounds and its grid resident;
+ * KeyFrame::GetFeaturesInArea, KeyFrame.cc:774-809, is Frame::GetFeaturesInArea without level
+ * arguments; a match frame without u_right has no stereo keypoint).  view[k] (20 floats): Rcw
+ * row-major (9), tcw (3), Ow (3), fx, fy, cx, cy, bf, as the caller's matrix types give them (for
+ * the Sim3 form the caller decomposes Scw).  Per point: world[3], normal[3], the raw mfMinDistance
+ * and mfMaxDistance, the 32-byte descriptor.  skip [n_kf][n_pts] or NULL: a non-zero pair is not
+ * searched.  scale_factors / inv_level_sigma2 [n_levels] = mvScaleFactors / mvInvLevelSigma2;
+ * log_scale_factor = mfLogScaleFactor.
+ *
+ * Semantics per pair (k, i): float32, each operation rounded once, nothing fused.
+ *   Pc_j = ((R[j][0]*P0 + R[j][1]*P1) + R[j][2]*P2) + t_j; culled if Pc_z < 0.
+ *   invz = 1/Pc_z; x = Pc_x*invz; y = Pc_y*invz; u = fx*x + cx; v = fy*y + cy; ur = u - bf*invz;
+ *   culled unless u >= min_x && u < max_x && v >= min_y && v < max_y (KeyFrame::IsInImage; a NaN is
+ *   culled by this test, as in the reference).
+ *   PO = P - Ow; dist = sqrt((PO0*PO0 + PO1*PO1) + PO2*PO2); culled if dist < 0.8f*min_dist ||
+ *   dist > 1.2f*max_dist; culled if ((PO0*n0 + PO1*n1) + PO2*n2) < 0.5f*dist.
+ *   ratio = max_dist / dist; level = the number of ygzfe_predict_scale_thresholds entries <= ratio
+ *   (= PredictScale clamped to [0, n_levels-1]).  Deviation: a pair whose dist or ratio is not a
+ *   finite positive number is culled (the reference converts a non-finite float to int there).
+ *   radius = th * scale_factors[level]; the window is GetFeaturesInArea(u, v, radius): the cell
+ *   range of :778-792 and strict |dx| < r && |dy| < r.
+ *   Candidate idx is kept when its octave is level-1 or level (:833) and, with check_reproj
+ *   (:836-860), where u_right[idx] >= 0: e2 = ((ex*ex + ey*ey) + er*er) with ex = u - x, ey = v - y,
+ *   er = ur - u_right[idx], rejected when (double)(e2*inv_level_sigma2[octave]) > 7.8; otherwise
+ *   e2 = ex*ex + ey*ey against 5.99.  check_reproj = 0 is the Sim3 form's search (:970-987).
+ *   The best candidate has the smallest Hamming distance; among equals the first in
+ *   GetFeaturesInArea order (cell-major ix*48 + iy, then ascending index) wins (`dist < bestDist`).
+ *
+ * best_idx [n_kf][n_pts]: that keypoint when bestDist <= 50 (TH_LOW), else -1; best_dist: the
+ * distance, or 256 when no candidate was kept.  Culled and skipped pairs give -1 / 256.  Each pair
+ * has its own slot: results are the same on every run.
+ * YGZFE_EINVAL, before anything is launched or written: n_levels outside [1, 16], a
+ * log_scale_factor that is not finite and positive, a keypoint octave outside [0, n_levels), frames
+ * on different devices, a null required pointer, more than 2^30 pairs.  n_kf == 0, n_pts == 0 and a
+ * keyframe with no keypoints are valid. */
+int ygzfe_fuse_search_batch(int n_kf, ygzfe_match_frame *const *kf, const float *view, int n_pts, const float *world,
+                            const float *normal, const float *min_dist, const float *max_dist, const uint8_t *desc,
+                            const uint8_t *skip, float th, const float *scale_factors, const float *inv_level_sigma2,
+                            int n_levels, float log_scale_factor, int check_reproj, int32_t *best_idx,
+                            int32_t *best_dist);
+/* The same for one keyframe (n_kf = 1): view[20], skip[n_pts] or NULL, best_idx / best_dist [n_pts]. */
+int ygzfe_fuse_search(ygzfe_match_frame *kf, const float *view, int n_pts, const float *world, const float *normal,
+                      const float *min_dist, const float *max_dist, const uint8_t *desc, const uint8_t *skip, float th,
+                      const float *scale_factors, const float *inv_level_sigma2, int n_levels, float log_scale_factor,
+                      int check_reproj, int32_t *best_idx, int32_t *best_dist);
+
 /* ------------------------------------------------------------------------ */
 /* SparseImgAlign (SparseImageAlign.h:37-60)                                 */
 typedef struct ygzfe_align_result {

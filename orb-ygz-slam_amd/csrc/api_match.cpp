@@ -1,6 +1,7 @@
 // api_match.cpp — the match-frame handle and the ORBmatcher searches over it.
 #include <string.h>
 
+#include <cmath>
 #include "host.hpp"
 
 // --------------------------------------------------------------------------
@@ -564,4 +565,150 @@ extern "C" int ygzfe_search_for_triangulation(
     return ygzfe_search_for_triangulation_batch(kf1, has_mp1, n1_nodes, nodes1, ptr1, feats1, 1, &kf2, mp2_ptr, has_mp2,
                                                 fv2_ptr, nodes2, ptr2, feats2, F12, epipole, level_sigma2,
                                                 scale_factors, n_levels, only_stereo, check_ori, matches12, nmatches);
+}
+
+// MapPoint::PredictScale (MapPoint.cc:343-357) as a table: nScale >= L  <=>  ratio >= thr[L - 1].  Positive
+// floats are ordered like their bit patterns, so the smallest one that reaches level L is found by bisection
+// over the bits, evaluating the reference's own expression (float logf, float divide, float ceil).
+namespace {
+bool reaches_level(float ratio, float log_scale_factor, int L) {
+    return ceilf(logf(ratio) / log_scale_factor) >= (float)L;
+}
+float bits_float(uint32_t b) {
+    float f;
+    memcpy(&f, &b, sizeof(f));
+    return f;
+}
+}  // namespace
+
+extern "C" int ygzfe_predict_scale_thresholds(float log_scale_factor, int n_levels, float *thr) {
+    if (!thr || n_levels < 1 || n_levels > 16 || !(log_scale_factor > 0.0f) || !std::isfinite(log_scale_factor)) {
+        set_error("invalid argument");
+        return YGZFE_EINVAL;
+    }
+    for (int L = 1; L < n_levels; L++) {
+        uint32_t lo = 1u, hi = 0x7F7FFFFFu;  // smallest subnormal .. FLT_MAX
+        if (!reaches_level(bits_float(hi), log_scale_factor, L)) {
+            thr[L - 1] = INFINITY;  // no finite ratio reaches the level
+            continue;
+        }
+        if (reaches_level(bits_float(lo), log_scale_factor, L)) hi = lo;
+        while (hi - lo > 1) {  // !reaches(lo) && reaches(hi)
+            const uint32_t mid = lo + (hi - lo) / 2;
+            (reaches_level(bits_float(mid), log_scale_factor, L) ? hi : lo) = mid;
+        }
+        thr[L - 1] = bits_float(hi);
+    }
+    return YGZFE_OK;
+}
+
+// ORBmatcher::Fuse's search for n_kf keyframes x n_pts map points: the argument checks and the threshold
+// table on the host, then one packed H2D, k_fuse_search, one D2H.
+extern "C" int ygzfe_fuse_search_batch(int n_kf, ygzfe_match_frame *const *kf, const float *view, int n_pts,
+                                       const float *world, const float *normal, const float *min_dist,
+                                       const float *max_dist, const uint8_t *desc, const uint8_t *skip, float th,
+                                       const float *scale_factors, const float *inv_level_sigma2, int n_levels,
+                                       float log_scale_factor, int check_reproj, int32_t *best_idx,
+                                       int32_t *best_dist) {
+    if (n_kf < 0 || n_pts < 0 || !scale_factors || !inv_level_sigma2 || (n_kf > 0 && (!kf || !view)) ||
+        (n_pts > 0 && (!world || !normal || !min_dist || !max_dist || !desc)) ||
+        (n_kf > 0 && n_pts > 0 && (!best_idx || !best_dist))) {
+        set_error("invalid argument");
+        return YGZFE_EINVAL;
+    }
+    if (n_levels < 1 || n_levels > 16) { set_error("n_levels %d outside [1, 16]", n_levels); return YGZFE_EINVAL; }
+    if (!(log_scale_factor > 0.0f) || !std::isfinite(log_scale_factor)) {
+        set_error("log_scale_factor must be finite and positive");
+        return YGZFE_EINVAL;
+    }
+    if ((long long)n_kf * n_pts > (1ll << 30)) { set_error("%d x %d pairs exceed 2^30", n_kf, n_pts); return YGZFE_EINVAL; }
+    for (int k = 0; k < n_kf; k++) {
+        const ygzfe_match_frame *f = kf[k];
+        if (!f) { set_error("keyframe %d is null", k); return YGZFE_EINVAL; }
+        if (f->device != kf[0]->device) { set_error("frames on different devices"); return YGZFE_EINVAL; }
+        for (int i = 0; i < f->n; i++)  // the level filter and inv_level_sigma2 are indexed by the octave
+            if (f->host_kps[i].octave < 0 || f->host_kps[i].octave >= n_levels) {
+                set_error("keyframe %d keypoint %d: octave %d outside [0, %d)", k, i, f->host_kps[i].octave, n_levels);
+                return YGZFE_EINVAL;
+            }
+    }
+    if (n_kf == 0 || n_pts == 0) return YGZFE_OK;
+    float thr[16] = {0};  // all 16 are uploaded
+    YGZ_TRY(ygzfe_predict_scale_thresholds(log_scale_factor, n_levels, thr));
+    StagingLease S;
+    YGZ_TRY(S.acquire(kf[0]->device));
+    // in: [keyframe table][desc][world][normal][min][max][thr][scale][inv sigma2][skip]   out: [best_idx][best_dist]
+    const size_t n_out = (size_t)n_kf * n_pts;
+    BlockLayout in{16}, out{16};
+    const size_t o_kf = in.take(n_kf, sizeof(FuseKf)), o_d = in.take(n_pts, 32), o_w = in.take(n_pts, 12);
+    const size_t o_n = in.take(n_pts, 12), o_mn = in.take(n_pts, 4), o_mx = in.take(n_pts, 4), o_thr = in.take(16, 4);
+    const size_t o_sc = in.take(n_levels, 4), o_sig = in.take(n_levels, 4), o_sk = skip ? in.take(n_out) : 0;
+    const size_t in_bytes = in.size();
+    const size_t o_bi = out.take(n_out, 4), o_bd = out.take(n_out, 4), out_bytes = out.size();
+    YGZ_TRY(S.reserve(in_bytes, out_bytes));
+    uint8_t *h = S->hin.as<uint8_t>(), *d = S->dev.as<uint8_t>(), *dout = d + in_bytes;
+    FuseKf *tab = at<FuseKf>(h, o_kf);
+    for (int k = 0; k < n_kf; k++) {
+        const ygzfe_match_frame *f = kf[k];
+        // the frame's upload and grid (asynchronous on its own stream) come first
+        if (f->ev_ready) YGZ_HIP(hipStreamWaitEvent(S->stream, f->ev_ready, 0));
+        FuseKf &K = tab[k];
+        K.kps = f->kps.as<ygzfe_kp>();
+        K.desc = f->desc.as<uint8_t>();
+        K.u_right = f->has_uright ? f->uright.as<float>() : nullptr;
+        K.cend = f->cell.as<int32_t>() + f->n;
+        K.cidx = reinterpret_cast<const uint16_t *>(K.cend + kMatchCells);
+        K.n = f->n;
+        K.min_x = f->bounds.min_x;
+        K.max_x = f->bounds.max_x;
+        K.min_y = f->bounds.min_y;
+        K.max_y = f->bounds.max_y;
+        K.inv_w = f->inv_w;
+        K.inv_h = f->inv_h;
+        memcpy(K.view, view + 20 * (size_t)k, sizeof(K.view));
+    }
+    memcpy(h + o_d, desc, (size_t)n_pts * 32);
+    memcpy(h + o_w, world, (size_t)n_pts * 12);
+    memcpy(h + o_n, normal, (size_t)n_pts * 12);
+    memcpy(h + o_mn, min_dist, (size_t)n_pts * 4);
+    memcpy(h + o_mx, max_dist, (size_t)n_pts * 4);
+    memcpy(h + o_thr, thr, sizeof(thr));
+    memcpy(h + o_sc, scale_factors, (size_t)n_levels * 4);
+    memcpy(h + o_sig, inv_level_sigma2, (size_t)n_levels * 4);
+    if (skip) memcpy(h + o_sk, skip, n_out);
+    YGZ_TRY(S.upload(in_bytes));
+    FuseJob J;
+    J.kf = at<const FuseKf>(d, o_kf);
+    J.n_kf = n_kf;
+    J.n_pts = n_pts;
+    J.world = at<const float>(d, o_w);
+    J.normal = at<const float>(d, o_n);
+    J.min_dist = at<const float>(d, o_mn);
+    J.max_dist = at<const float>(d, o_mx);
+    J.desc = d + o_d;
+    J.skip = skip ? d + o_sk : nullptr;
+    J.thr = at<const float>(d, o_thr);
+    J.scale_factors = at<const float>(d, o_sc);
+    J.inv_level_sigma2 = at<const float>(d, o_sig);
+    J.th = th;
+    J.n_levels = n_levels;
+    J.check_reproj = check_reproj != 0;
+    J.best_idx = at<int32_t>(dout, o_bi);
+    J.best_dist = at<int32_t>(dout, o_bd);
+    YGZ_HIP(launch_fuse_search(J, S->stream));
+    YGZ_TRY(S.download(in_bytes, out_bytes));
+    memcpy(best_idx, S->hout.as<uint8_t>() + o_bi, n_out * 4);
+    memcpy(best_dist, S->hout.as<uint8_t>() + o_bd, n_out * 4);
+    return YGZFE_OK;
+}
+
+extern "C" int ygzfe_fuse_search(ygzfe_match_frame *kf, const float *view, int n_pts, const float *world,
+                                 const float *normal, const float *min_dist, const float *max_dist,
+                                 const uint8_t *desc, const uint8_t *skip, float th, const float *scale_factors,
+                                 const float *inv_level_sigma2, int n_levels, float log_scale_factor,
+                                 int check_reproj, int32_t *best_idx, int32_t *best_dist) {
+    if (!kf) { set_error("invalid argument"); return YGZFE_EINVAL; }
+    return ygzfe_fuse_search_batch(1, &kf, view, n_pts, world, normal, min_dist, max_dist, desc, skip, th,
+                                   scale_factors, inv_level_sigma2, n_levels, log_scale_factor, check_reproj,
+                                   best_idx, best_dist);
 }

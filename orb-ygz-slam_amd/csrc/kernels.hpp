@@ -132,6 +132,30 @@ struct TriJob {
 };
 hipError_t launch_triangulation(const TriJob &J, hipStream_t st);
 
+// ORBmatcher::Fuse's search (ORBmatcher.cc:748-866), n_kf keyframes x n_pts map points
+struct FuseKf {  // one target keyframe: its match frame's device arrays, bounds and view
+    const ygzfe_kp *kps;
+    const uint8_t *desc;
+    const float *u_right;  // null: no keypoint is stereo
+    const int32_t *cend;
+    const uint16_t *cidx;
+    int32_t n;
+    float min_x, max_x, min_y, max_y, inv_w, inv_h;
+    float view[20];  // Rcw row-major, tcw, Ow, fx, fy, cx, cy, bf
+};
+struct FuseJob {
+    const FuseKf *kf;
+    int n_kf, n_pts;
+    const float *world, *normal, *min_dist, *max_dist;  // [n_pts][3], [n_pts][3], [n_pts], [n_pts]
+    const uint8_t *desc;                                // [n_pts][32], 16-byte aligned
+    const uint8_t *skip;                                // [n_kf][n_pts] or null
+    const float *thr, *scale_factors, *inv_level_sigma2;  // [n_levels - 1], [n_levels], [n_levels]
+    float th;
+    int n_levels, check_reproj;
+    int32_t *best_idx, *best_dist;  // [n_kf][n_pts]
+};
+hipError_t launch_fuse_search(const FuseJob &F, hipStream_t st);
+
 // align.hip
 struct AlignLevels {
     int w[kMaxLevels], h[kMaxLevels];

@@ -7,6 +7,7 @@
 //   SearchByBoW(pKF, F, vpMapPointMatches)                             :155-263    mode BOW
 //   ComputeThreeMaxima                                                 :1471-1502
 //   SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo) :597-746   (the mapping side; at the end)
+//   Fuse(pKF, vpMapPoints, th) / Fuse(pKF, Scw, ...)'s search            :748-1004  (the mapping side; at the end)
 //
 // The reference runs one query after another, and a query's candidates
 // depend on the assignments of the queries before it (a keypoint matched to
@@ -1053,6 +1054,122 @@ hipError_t launch_triangulation(const TriJob &J, hipStream_t st) {
         hipLaunchKernelGGL(k_tri_search, dim3((J.n_rows + groups - 1) / groups), dim3(kTriThreads), 0, st, J);
     }
     if (J.n_nb > 0) hipLaunchKernelGGL(k_tri_votes, dim3(J.n_nb), dim3(kTriThreads), 0, st, J);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// ORBmatcher::Fuse(pKF, vpMapPoints, th) (ORBmatcher.cc:748-886; the Sim3 form :888-1004 without the
+// reprojection gate): the search of every (keyframe, map point) pair of a SearchInNeighbors phase.  A pair
+// reads only the keyframe and the point, so the pairs are independent; the map surgery that follows
+// (:868-882) stays with the host, which replays it in the reference's order from best_idx / best_dist.
+//
+//  k_fuse_search  one wave per pair, one launch.  The projection (:768-811) is ~40 float operations on
+//                 wave-uniform values, cheaper than writing survivors to a list and reading them back in
+//                 a second launch; a culled pair's wave stores its slot and retires.  PredictScale is
+//                 a count over the host's threshold table (no device log: see ygzfe.h).  Then lanes over
+//                 the GetFeaturesInArea window (for_window), the octave filter and the reprojection gate
+//                 on each candidate, and a wave minimum over the (distance, cell, index) keys.  Each
+//                 pair writes its own slot: no compaction, no atomics, the same result on every run.
+constexpr int kFuseWaves = 4;
+constexpr int kFuseThLow = 50;  // ORBmatcher::TH_LOW
+
+__global__ __launch_bounds__(64 * kFuseWaves) void k_fuse_search(const FuseJob F) {
+    const int pair = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * kFuseWaves + (threadIdx.x >> 6)));
+    if (pair >= F.n_kf * F.n_pts) return;
+    const int lane = threadIdx.x & 63;
+    const int k = pair / F.n_pts, i = pair - k * F.n_pts;
+    const FuseKf &K = F.kf[k];
+    int out_idx = -1, out_dist = 256;
+    auto search = [&]() {
+        if (K.n == 0 || (F.skip && F.skip[pair])) return;
+        const float P0 = F.world[3 * i], P1 = F.world[3 * i + 1], P2 = F.world[3 * i + 2];
+        const float *R = K.view, *t = K.view + 9, *Ow = K.view + 12;
+        const float fx = K.view[15], fy = K.view[16], cx = K.view[17], cy = K.view[18], bf = K.view[19];
+        const float Pcx = ((R[0] * P0 + R[1] * P1) + R[2] * P2) + t[0];
+        const float Pcy = ((R[3] * P0 + R[4] * P1) + R[5] * P2) + t[1];
+        const float Pcz = ((R[6] * P0 + R[7] * P1) + R[8] * P2) + t[2];
+        if (Pcz < 0.0f) return;  // :771
+        const float invz = 1.0f / Pcz;
+        const float x = Pcx * invz, y = Pcy * invz;
+        const float u = fx * x + cx, v = fy * y + cy;
+        if (!(u >= K.min_x && u < K.max_x && v >= K.min_y && v < K.max_y)) return;  // IsInImage; NaN culled
+        const float ur = u - bf * invz;
+        const float PO0 = P0 - Ow[0], PO1 = P1 - Ow[1], PO2 = P2 - Ow[2];
+        const float dist3 = sqrtf((PO0 * PO0 + PO1 * PO1) + PO2 * PO2);
+        const float maxd = F.max_dist[i];
+        if (dist3 < 0.8f * F.min_dist[i] || dist3 > 1.2f * maxd) return;  // :797
+        if (((PO0 * F.normal[3 * i] + PO1 * F.normal[3 * i + 1]) + PO2 * F.normal[3 * i + 2]) < 0.5f * dist3) return;
+        const float ratio = maxd / dist3;
+        // the reference converts a non-finite float to int here: such a pair is culled instead
+        if (!(dist3 > 0.0f && dist3 < __builtin_inff() && ratio > 0.0f && ratio < __builtin_inff())) return;
+        int level = 0;  // PredictScale: thr[L - 1] <= ratio  <=>  ceil(logf(ratio) / lsf) >= L
+        for (int L = 1; L < F.n_levels; L++) level += F.thr[L - 1] <= ratio;
+        // Only what the window helpers read is set: make_window reads min_x, min_y, inv_w, inv_h; for_window reads
+        // cend and cidx; window_accept reads kps and, only under YGZFE_MQ_STEREO (not set here), u_right.
+        MatchJob J;
+        J.kps = K.kps;
+        J.u_right = nullptr;
+        J.cend = K.cend;
+        J.cidx = K.cidx;
+        J.min_x = K.min_x;
+        J.min_y = K.min_y;
+        J.inv_w = K.inv_w;
+        J.inv_h = K.inv_h;
+        ygzfe_match_query Q;
+        Q.u = u;
+        Q.v = v;
+        Q.radius = F.th * F.scale_factors[level];
+        Q.u_right = 0.f;
+        Q.min_level = Q.max_level = -1;  // GetFeaturesInArea(u, v, radius): no level arguments
+        Q.angle = 0.f;
+        Q.flags = 0;
+        const Window w = make_window(J, Q);
+        uint32_t qd[8];
+        {
+            const uint4 *p = reinterpret_cast<const uint4 *>(F.desc + (size_t)i * 32);
+            const uint4 a = p[0], b = p[1];
+            qd[0] = a.x; qd[1] = a.y; qd[2] = a.z; qd[3] = a.w;
+            qd[4] = b.x; qd[5] = b.y; qd[6] = b.z; qd[7] = b.w;
+        }
+        uint64_t best = ~0ull;
+        for_window(J, w, [&](int j, int c) {
+            const uint32_t order = window_accept(J, w, Q, j, c);
+            if (order == ~0u) return;
+            const ygzfe_kp kp = K.kps[j];
+            if (kp.octave < level - 1 || kp.octave > level) return;  // :833
+            if (F.check_reproj) {                                   // :836-860
+                const float ex = u - kp.x, ey = v - kp.y;
+                const float kpr = K.u_right ? K.u_right[j] : -1.0f;
+                if (kpr >= 0.0f) {
+                    const float er = ur - kpr;
+                    const float e2 = (ex * ex + ey * ey) + er * er;
+                    if ((double)(e2 * F.inv_level_sigma2[kp.octave]) > 7.8) return;
+                } else {
+                    const float e2 = ex * ex + ey * ey;
+                    if ((double)(e2 * F.inv_level_sigma2[kp.octave]) > 5.99) return;
+                }
+            }
+            const uint64_t key = make_key(hamming32(qd, K.desc + (size_t)j * 32), order, j, kp.octave);
+            best = key < best ? key : best;
+        });
+        best = wave_min_u64(best);
+        if (best != ~0ull) {
+            out_dist = (int)(best >> 52);
+            out_idx = out_dist <= kFuseThLow ? key_train(best) : -1;
+        }
+    };
+    search();
+    if (lane == 0) {
+        F.best_idx[pair] = out_idx;
+        F.best_dist[pair] = out_dist;
+    }
+}
+
+hipError_t launch_fuse_search(const FuseJob &F, hipStream_t st) {
+    const long long pairs = (long long)F.n_kf * F.n_pts;
+    if (pairs > 0)
+        hipLaunchKernelGGL(k_fuse_search, dim3((unsigned)((pairs + kFuseWaves - 1) / kFuseWaves)), dim3(64 * kFuseWaves),
+                           0, st, F);
     return hipGetLastError();
 }
 

@@ -562,6 +562,66 @@ def search_for_triangulation(kf1, kf2, has_mp1, fv1, has_mp2, fv2, F12, epipole,
     return m12, int(nm[0])
 
 
+def predict_scale_thresholds(log_scale_factor, n_levels):
+    """MapPoint::PredictScale (MapPoint.cc:343-357) as a table (host only): float32[n_levels - 1], thr[L-1] = the
+    smallest positive float r with ceil(logf(r) / log_scale_factor) >= L; the level of a ratio is the number of
+    thresholds <= ratio."""
+    thr = np.zeros(16, np.float32)
+    _check(lib().ygzfe_predict_scale_thresholds(float(log_scale_factor), int(n_levels), _p(thr)),
+           "predict_scale_thresholds")
+    return thr[:n_levels - 1].copy()
+
+
+def fuse_search_batch(kfs, views, world, normal, min_dist, max_dist, desc, scale_factors, inv_level_sigma2,
+                      log_scale_factor, skip=None, th=3.0, check_reproj=True, best_idx=None, best_dist=None):
+    """The search of ORBmatcher::Fuse (ORBmatcher.cc:748-866) for every (keyframe, map point) pair in one call
+    (LocalMapping::SearchInNeighbors).  kfs: MatchFrames; views [n_kf, 20] = Rcw row-major, tcw, Ow, fx, fy, cx, cy,
+    bf; world / normal [n_pts, 3]; min_dist / max_dist the raw mfMinDistance / mfMaxDistance; desc [n_pts, 32];
+    skip [n_kf, n_pts] or None; check_reproj=False is the Sim3 form's search.
+    -> (best_idx int32[n_kf, n_pts]: the keypoint when bestDist <= 50 else -1, best_dist int32[n_kf, n_pts]:
+    the distance, 256 when no candidate was kept).  best_idx / best_dist: arrays to write instead of new ones."""
+    n_kf = len(kfs)
+    w = np.ascontiguousarray(world, np.float32).reshape(-1, 3)
+    n_pts = len(w)
+    nrm = np.ascontiguousarray(normal, np.float32).reshape(-1, 3)
+    mn, mx = np.ascontiguousarray(min_dist, np.float32).ravel(), np.ascontiguousarray(max_dist, np.float32).ravel()
+    d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+    vw = np.ascontiguousarray(views, np.float32).reshape(-1, 20)
+    sc, sig = np.ascontiguousarray(scale_factors, np.float32), np.ascontiguousarray(inv_level_sigma2, np.float32)
+    if not (len(nrm) == len(mn) == len(mx) == len(d) == n_pts) or len(vw) != n_kf or len(sc) != len(sig):
+        raise ValueError("fuse_search_batch: array lengths disagree")
+    sk = None if skip is None else np.ascontiguousarray(skip, np.uint8).reshape(n_kf, n_pts)
+    hs = (C.c_void_p * max(n_kf, 1))(*[f.h.value for f in kfs])
+    bi = np.full((n_kf, n_pts), -2, np.int32) if best_idx is None else best_idx  # -2: not written
+    bd = np.full((n_kf, n_pts), -2, np.int32) if best_dist is None else best_dist
+    assert bi.dtype == bd.dtype == np.int32 and bi.size == bd.size == n_kf * n_pts and bi.flags.c_contiguous
+    _check(lib().ygzfe_fuse_search_batch(n_kf, hs, _p(vw), n_pts, _p(w), _p(nrm), _p(mn), _p(mx), _p(d),
+                                         None if sk is None else _p(sk), float(th), _p(sc), _p(sig), len(sc),
+                                         float(log_scale_factor), int(check_reproj), _p(bi), _p(bd)),
+           "fuse_search_batch")
+    return bi, bd
+
+
+def fuse_search(kf, view, world, normal, min_dist, max_dist, desc, scale_factors, inv_level_sigma2, log_scale_factor,
+                skip=None, th=3.0, check_reproj=True):
+    """ORBmatcher::Fuse's search for one keyframe -> (best_idx int32[n_pts], best_dist int32[n_pts])."""
+    w = np.ascontiguousarray(world, np.float32).reshape(-1, 3)
+    n_pts = len(w)
+    nrm = np.ascontiguousarray(normal, np.float32).reshape(-1, 3)
+    mn, mx = np.ascontiguousarray(min_dist, np.float32).ravel(), np.ascontiguousarray(max_dist, np.float32).ravel()
+    d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+    vw = np.ascontiguousarray(view, np.float32).reshape(20)
+    sc, sig = np.ascontiguousarray(scale_factors, np.float32), np.ascontiguousarray(inv_level_sigma2, np.float32)
+    if not (len(nrm) == len(mn) == len(mx) == len(d) == n_pts) or len(sc) != len(sig):
+        raise ValueError("fuse_search: array lengths disagree")
+    sk = None if skip is None else np.ascontiguousarray(skip, np.uint8).reshape(n_pts)
+    bi, bd = np.full(n_pts, -2, np.int32), np.full(n_pts, -2, np.int32)
+    _check(lib().ygzfe_fuse_search(kf.h, _p(vw), n_pts, _p(w), _p(nrm), _p(mn), _p(mx), _p(d),
+                                   None if sk is None else _p(sk), float(th), _p(sc), _p(sig), len(sc),
+                                   float(log_scale_factor), int(check_reproj), _p(bi), _p(bd)), "fuse_search")
+    return bi, bd
+
+
 class SparseImgAlign:
     """SparseImgAlign(n_levels, min_level, n_iter=10, method=GaussNewton) (SparseImageAlign.h:37-60)."""
     GaussNewton, LevenbergMarquardt = 0, 1  # NLLSSolver's methods (NLSSolver.h:40-43)

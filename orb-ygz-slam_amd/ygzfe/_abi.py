@@ -24,6 +24,7 @@ YGZFE = """
     match_frame_resolve_stats=i:pp match_frame_from_batch=i:ppip search_projection_best=i:pppipiipp
     search_projection_ratio=i:pppipfpp search_for_initialization=i:pppifipp search_by_bow=i:pppipppipppfipp
     search_for_triangulation_batch=i:ppipppipppppppppppiiipp search_for_triangulation=i:ppipppppipppppppiiipp
+    predict_scale_thresholds=i:fip fuse_search_batch=i:ippippppppfppifipp fuse_search=i:ppippppppfppifipp
     sparse_align=i:ppppppiiipp sparse_align_begin=i:ppppppiiip sparse_align_end=i:pp sparse_align_method=i:ppppppiiipip
     extractor_align_probe=i:ppp batch_sparse_align=i:pipppppiippp fast10_detect=i:ipiiipiiipip
     debug_dso_cells=i:ipiiiip align2d_batch=i:piippipp align2d_image=i:ipiiippipp
