@@ -733,7 +733,11 @@ int ygzfe_stereo_matches(const ygzfe_frame *left, const ygzfe_frame *right, cons
                          float *u_right, float *depth);
 /* Batched: pair p matches batch frame d_left_idx[p] (left eye) against
  * d_right_idx[p] (right eye), both extracted by ygzfe_batch_extract;
- * d_u_right / d_depth are [n_pairs][kp_cap] rows of the left frame's keypoints. */
+ * d_u_right / d_depth are [n_pairs][kp_cap] rows of the left frame's keypoints.
+ * Pair p writes rows [0, n_left) of its own output row p, n_left being the left
+ * frame's count, and leaves rows [n_left, kp_cap) as the caller set them.  A frame
+ * may be left in one pair and right in another, or both in one; a pair may be
+ * listed more than once; a frame without keypoints is valid on either side. */
 int ygzfe_batch_stereo(ygzfe_batch *b, int n_pairs, const int32_t *d_left_idx, const int32_t *d_right_idx,
                        float mb, float mbf, float *d_u_right, float *d_depth, void *stream);
 /* Frame::ComputeStereoFromRGBD (Frame.cc:684-700): d = imDepth(int v, int u)
@@ -741,7 +745,9 @@ int ygzfe_batch_stereo(ygzfe_batch *b, int n_pairs, const int32_t *d_left_idx, c
 int ygzfe_stereo_from_rgbd(int device, const float *im_depth, int width, int height, int stride,
                            const ygzfe_kp *kps, int n, float mbf, float *u_right, float *depth);
 /* Batched over the first n_frames frames of a batch: depth image f at
- * d_depth_images + f * depth_pitch (floats); outputs [n_frames][kp_cap]. */
+ * d_depth_images + f * depth_pitch (floats), rows `stride` >= width floats apart;
+ * outputs [n_frames][kp_cap], of which frame f writes the rows below its count
+ * and leaves the others as the caller set them. */
 int ygzfe_batch_stereo_rgbd(ygzfe_batch *b, int n_frames, const float *d_depth_images, size_t depth_pitch,
                             int stride, float mbf, float *d_u_right, float *d_depth, void *stream);
 

@@ -184,6 +184,13 @@ class Frame(_Handle):
         img = np.ascontiguousarray(img, np.uint8)
         _check(lib().ygzfe_frame_set_level(self.h, l, _p(img), img.shape[1]), "frame_set_level")
 
+    def set_levels(self, imgs, first=0):
+        """Upload levels [first, first + len(imgs)) of a host pyramid in one DMA (ygzfe_frame_set_levels)."""
+        imgs = [np.ascontiguousarray(im, np.uint8) for im in imgs]
+        src = (C.c_void_p * len(imgs))(*[im.ctypes.data for im in imgs])
+        strides = (C.c_int * len(imgs))(*[im.shape[1] for im in imgs])
+        _check(lib().ygzfe_frame_set_levels(self.h, first, len(imgs), src, strides), "frame_set_levels")
+
     def set_keypoints(self, kps):
         """A keyframe's mvKeys, resident with the frame (read by search_local_map_direct)."""
         kps = np.ascontiguousarray(kps, KP_DTYPE)
